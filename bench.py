@@ -14,12 +14,19 @@ Other driver-reproducible modes:
     --cells-per-gpu 10000000 --batches 20          north_star target: 10M x 50 x K=100 on ONE GPU (configs[3]'s size)
     --workload c5 [--cells-per-gpu N]              configs[4] shape: K=200, 3 nested covariates 8 > 64 > 128 (200 levels)
     --total-cells 10000000 --batches 20 --gpus N   STRONG scaling: configs[3] = 10M cells in total, sharded over the N GPUs
-    --also ref,10M,share,c5,pbmc (default at N=1 incl. ref2 = "ref_arith" 2; "none"; "shares": the per-rank shares of the 8-GPU configs at G = 2 / 4 / 8)  extra legs of the same invocation, reported under "also": the reference-arithmetic
+    --full                                         everything beyond the headline figure (below); a plain run only sets up, warms up, times
+                                                   --steps runs, writes --dump-outputs and prints the line
+    --full --also ref,10M,share,c5,pbmc (default at N=1 incl. ref2 = "ref_arith" 2; "none"; "shares": the per-rank shares of the 8-GPU configs at G = 2 / 4 / 8)  extra legs of the same invocation, reported under "also": the reference-arithmetic
                                                    mode on the main workload, 10M cells on this one GPU, the configs[4] shape at 1M,
                                                    configs[1] (pbmc, 30k cells) with its own CPU-oracle timing and parity check
+    --dump-outputs DIR                             after the timed steps: what the last timed step computed, as DIR/<name>.npy (below)
 
 A "step" = one full run from HBM-resident inputs: hmx_restart -> init_cluster_cpp (k-means seeding + 10 Lloyd)
 -> {cluster_cpp, moe_correct_ridge_cpp, check_convergence}* until converged.  Prints ONE JSON line (rank 0).
+
+Only with --full: the per-phase table (one extra untimed run), T_e2e (ingest / egress over PCIe, a second setup), the `also` legs, the
+weak-scaling companion of the default N > 1 line, the CPU baseline (--cpu-sample / --cpu-full), the replayed parity table and scaling
+prediction.  The roofline and the chain's counters come from the timed launches themselves and are in every line.
 """
 import argparse
 import json
@@ -51,6 +58,44 @@ def run_to_convergence(obj, max_iter=10):
     return it
 
 
+DUMP_BYTES = 48 << 20      # the sampled per-cell matrices of --dump-outputs (the rest are K x B / d x K tables and per-iteration series)
+DUMP_SEED = 20240611       # fixed: the same cells are sampled by every build and every run
+
+
+def dump_outputs(obj, out_dir, iters, cell_offset=0):
+    """--dump-outputs DIR: what the last timed step computed, as a caller of the step receives it -- Z_corr (d x cells) and R (K x cells),
+    the centroids Y, the O / E tables, the objective series, the rounds per harmony iteration -- read back after the timed region.  The
+    per-cell matrices are a fixed, seeded sample of cells (all cells when they fit DUMP_BYTES), their global indices in sample_cells.npy;
+    float32 as the library holds them, the host-side series float64.  In a sharded run rank 0 writes its own cells."""
+    os.makedirs(out_dir, exist_ok=True)
+    n, d, K = int(obj._scalar("N_local")), int(obj.d), int(obj.K)
+    m = min(n, DUMP_BYTES // (4 * (d + K)))
+    cols = np.arange(n) if m == n else np.sort(np.random.Generator(np.random.Philox(key=DUMP_SEED)).choice(n, size=m, replace=False))
+    arrays = {"Z_corr": np.ascontiguousarray(obj.get_matrix("Z_corr", np.float32)[:, cols]),
+              "R": np.ascontiguousarray(obj.get_matrix("R", np.float32)[:, cols]),
+              "sample_cells": (cols + cell_offset).astype(np.float64),
+              "Y": np.asarray(obj.Y, dtype=np.float64), "O": np.asarray(obj.O, dtype=np.float64), "E": np.asarray(obj.E, dtype=np.float64),
+              "objective_kmeans": np.asarray(obj.objective_kmeans, dtype=np.float64),
+              "objective_harmony": np.asarray(obj.objective_harmony, dtype=np.float64),
+              "kmeans_rounds": np.asarray(obj.kmeans_rounds, dtype=np.float64),
+              "harmony_iterations": np.asarray(iters, dtype=np.float64)}
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+    return sorted(arrays)
+
+
+def host_threads():
+    """CPUs this process may use for the CPU baseline: its affinity mask, capped by the thread count the environment gives the BLAS.  The
+    bundled OpenBLAS sizes its thread pool once, at load, from OPENBLAS_NUM_THREADS / GOTO_NUM_THREADS / OMP_NUM_THREADS or the CPU
+    count (at most 64, its build's MAX_THREADS), and segfaults in the next sgemm when set_num_threads later asks for more."""
+    n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    for v in ("OPENBLAS_NUM_THREADS", "GOTO_NUM_THREADS", "OMP_NUM_THREADS"):
+        s = os.environ.get(v, "").strip()
+        if s.isdigit() and int(s) > 0:
+            return max(1, min(n, int(s), 64))
+    return max(1, min(n, 64))
+
+
 def cpu_baseline(cells, d, K, levels, nested, seed):
     """The oracle (a port: the reference itself cannot be built here) in faithful fp32 mode on a bounded sample of the same
     workload, GEMM through OpenBLAS: 1 thread (the reference's default ncores = 1, R/ui.R:101) = `value`; and all host cores
@@ -61,7 +106,7 @@ def cpu_baseline(cells, d, K, levels, nested, seed):
     Z, meta, _ = synth(cells, d=d, levels=levels, seed=seed, nested=nested)
     skw, _ = prepare_setup_args(Z, meta, list(meta), nclust=K)
     out = {}
-    ncpu = os.cpu_count() or 1
+    ncpu = host_threads()
     for tag, threads in (("one", 1), ("all", ncpu)):
         blas = use_openblas(threads)
         o = OracleHarmony(accurate=False, seed=1)
@@ -344,7 +389,7 @@ def main_file_bootstrap(a):
     (spawned here if no launcher did: RANK / LOCAL_RANK / WORLD_SIZE in the environment), rank 0 creates the RCCL unique id
     (hmx_comm_unique_id) and passes it through a file, hmx_comm_init builds the communicator and connects + self-tests the peers' inboxes,
     barriers / max-over-ranks / the sanity sums go through hmx_comm_allreduce_host.  Same step, same JSON contract as the default path; the
-    single-GPU extras (e2e, `also` legs, CPU baseline) stay with the default invocation."""
+    single-GPU extras (e2e, `also` legs, CPU baseline) stay with the default invocation's --full."""
     import tempfile
     world = int(os.environ.get("WORLD_SIZE", str(a.gpus)))
     if a.gpus > 1 and "RANK" not in os.environ:
@@ -413,6 +458,8 @@ def main_file_bootstrap(a):
     if world > 1:
         dt = float(obj.comm_allreduce_host([dt], "max")[0])
     ms_per_step = 1e3 * dt / a.steps
+    if a.dump_outputs and rank == 0:
+        dump_outputs(obj, a.dump_outputs, iters, rank * n)
     shard_check = None
     if world > 1:
         O = np.ascontiguousarray(obj.O, dtype=np.float64).ravel()
@@ -555,15 +602,19 @@ def main():
     ap.add_argument("--cells-per-gpu", type=int, default=None, help="weak scaling: this many cells on EVERY GPU (default at --gpus 1: 1000000 = configs[2])")
     ap.add_argument("--total-cells", type=int, default=0, help="strong scaling: this many cells in TOTAL, sharded over --gpus (overrides --cells-per-gpu); "
                     "default at --gpus N > 1 when no size is given: 10000000 with --batches 20 = BASELINE configs[3]")
-    ap.add_argument("--also", default=None, help="extra legs at N=1, comma separated: ref (reference arithmetic on the main workload), 10M, share (1.25M cells / 20 batches: one GPU's part of configs[3] on 8), c5, pbmc "
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beyond the headline figure: per-phase table, T_e2e, the `also` legs, "
+                    "the weak-scaling companion of the default N > 1 line, CPU baseline, replayed parity table and scaling prediction (off: a plain run)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the last timed step computed as DIR/<name>.npy "
+                    "(float32 / float64, at most ~50 MB: a fixed, seeded sample of the cells)")
+    ap.add_argument("--also", default=None, help="with --full: extra legs at N=1, comma separated: ref (reference arithmetic on the main workload), 10M, share (1.25M cells / 20 batches: one GPU's part of configs[3] on 8), c5, pbmc "
                     "(configs[1] at its stated size, with its own CPU oracle timing); default 'ref,10M,share,c5,pbmc' for the default workload on one GPU, 'none' otherwise")
     ap.add_argument("--pcs", type=int, default=50)
     ap.add_argument("--clusters", type=int, default=None)
     ap.add_argument("--batches", type=int, default=None, help="levels of the one covariate (default 10 = configs[2]; 20 with the configs[3] default of --gpus N > 1)")
-    ap.add_argument("--cpu-sample", type=int, default=100000, help="cells for the CPU baseline (0 = skip)")
-    ap.add_argument("--cpu-full", action="store_true", help="time the CPU baseline at the FULL workload size in this run (~1 min at 1M cells) instead of replaying the committed figure")
+    ap.add_argument("--cpu-sample", type=int, default=None, help="with --full: cells for the CPU baseline (default 100000; 0 = skip)")
+    ap.add_argument("--cpu-full", action="store_true", help="with --full: time the CPU baseline at the FULL workload size in this run (~1 min at 1M cells) instead of replaying the committed figure")
     ap.add_argument("--seed", type=int, default=7)
-    ap.add_argument("--no-e2e", action="store_true", help="skip the T_e2e measurement (ingest + egress over PCIe)")
+    ap.add_argument("--no-e2e", action="store_true", help="with --full: skip the T_e2e measurement (ingest + egress over PCIe)")
     ap.add_argument("--pmc", action="store_true", help="N = 1: collect the dominant kernel's HBM traffic and MFMA-busy counters with rocprofv3 first (three separate "
                     "--pmc passes, ~1 minute) and refresh profiles/pmc_traffic_update_kernel.json, which the roofline's `traffic` is read from")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N>1 (nccl == RCCL; gloo only for smoke tests on one GPU)")
@@ -571,6 +622,12 @@ def main():
                     "file: no torch in the process -- unique id through a file, hmx_comm_init, host reductions through the library")
     a = ap.parse_args()
     apply_size_defaults(a)
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not a.full and ((a.also or "none") != "none" or a.cpu_full or (a.cpu_sample or 0) > 0):
+        ap.error("--also / --cpu-sample / --cpu-full shape the extra measurements of --full: add --full")
+    if a.cpu_sample is None:
+        a.cpu_sample = 100000 if a.full else 0
 
     if a.bootstrap == "file":
         return main_file_bootstrap(a)
@@ -782,13 +839,17 @@ def main():
     ms_per_step = 1e3 * dt / a.steps
     prof = {k: obj._scalar("prof:" + k) for k in ("update_ms", "update_launches", "update_cells", "update_steps")}
     kr_timed = np.asarray(obj.kmeans_rounds, dtype=np.int64)
-    obj.set_profile(2)
-    run_to_convergence(obj)
-    sync()
-    gpu_phase = {k: round(obj._scalar("gputimer:" + k), 3) for k in
-                 ("kmeans_centers", "cluster_head", "randomize", "EO_update", "correct_ridge_loop", "ridge_statistics", "arma_inv", "update_Zcorr")}
-    gpu_phase["Rcells_update"] = round(prof["update_ms"] / a.steps, 3)
-    gpu_phase["from"] = "one extra untimed run with per-phase event brackets (Rcells_update: the timed runs' own launch events)"
+    if a.dump_outputs and rank == 0:
+        dump_outputs(obj, a.dump_outputs, iters, rank * n)
+    gpu_phase = None
+    if a.full:
+        obj.set_profile(2)
+        run_to_convergence(obj)
+        sync()
+        gpu_phase = {k: round(obj._scalar("gputimer:" + k), 3) for k in
+                     ("kmeans_centers", "cluster_head", "randomize", "EO_update", "correct_ridge_loop", "ridge_statistics", "arma_inv", "update_Zcorr")}
+        gpu_phase["Rcells_update"] = round(prof["update_ms"] / a.steps, 3)
+        gpu_phase["from"] = "one extra untimed run with per-phase event brackets (Rcells_update: the timed runs' own launch events)"
     shard_check = None
     if world > 1:
         # sharded sanity: every rank holds the same global O (integer sums) and it accounts for every cell (once per covariate: sum O = C N)
@@ -877,7 +938,7 @@ def main():
                 chain[nm + "_phases_us"] = {p_: round(float(dbg[o + i]) / 100.0 / steps_, 3) for i, p_ in enumerate(ph)}
     # T_e2e: T_conv + H2D of Z (double, the R seam) + D2H of Z_corr (double); PCIe-inclusive, never `value`
     e2e = None
-    if not a.no_e2e:
+    if a.full and not a.no_e2e:
         sync()
         t1 = time.perf_counter()
         zc = obj.getZcorr()
@@ -925,17 +986,17 @@ def main():
                                             else "configs[4] shape" if a.workload == "c5" else "user-sized")
         out["parity_mode"] = ("default: exact accumulators, identical for every shard count (integer sums); parity target = the reference's own sources built with its "
                               "-DHARMONY_SCALAR_DOUBLE switch (INTEGRATION.md, 'Which result a sharded run returns'); reference arithmetic is a one-GPU mode")
-        try:      # DESIGN 5.2's prediction for this very line, made before any run crossed two devices: the hardware run falsifies or confirms it
+        try:      # (--full) DESIGN 5.2's prediction for this very line, made before any run crossed two devices: the hardware run falsifies or confirms it
             pfile = next(f for f in ("r6_scaling_prediction.json", "r5_scaling_prediction.json") if os.path.exists(os.path.join(ROOT, "profiles", f)))
             pj = json.load(open(os.path.join(ROOT, "profiles", pfile)))
             key = "configs3" if (N, d, K, levels) == (10000000, 50, 100, (20,)) else ("configs4" if a.workload == "c5" and N == 5000000 else None)
-            if key and str(world) in pj[key]:
+            if a.full and key and str(world) in pj[key]:
                 e = pj[key][str(world)]
                 out["predicted"] = {"ms_per_step": e["predicted_ms"], "speedup_vs_1_gpu": e["speedup_vs_1"], "one_rank_share_without_exchanges_ms": e["share_ms"],
                                     "source": "profiles/%s (tools/scaling_prediction.py: per-rank shares measured on ONE GPU + measured one-device exchange costs)" % pfile}
         except Exception:
             pass
-        if a.default_multi and (a.also or "weak") != "none":
+        if a.full and a.default_multi and (a.also or "weak") != "none":
             # the weak-scaling companion of the default N > 1 line: configs[2]'s 1M cells x 10 batches on EVERY GPU
             try:
                 del obj
@@ -957,11 +1018,11 @@ def main():
                 del o2
             except Exception as e:     # pragma: no cover  (an extra leg never costs the main line)
                 out["also"] = {"weak_scaling_1M_per_gpu": {"error": repr(e)}}
-    hp = headline_parity(n, d, K, levels) if world == 1 else None
+    hp = headline_parity(n, d, K, levels) if (a.full and world == 1) else None
     if hp:
         out.update({"parity_mode": hp["parity_mode"], "Z_rel_vs_accurate": hp["Z_rel_vs_accurate"], "Z_rel_vs_faithful": hp["Z_rel_vs_faithful"], "parity": hp})
     default_main = world == 1 and a.workload == "c3" and n == 1000000 and levels == (10,) and K == 100 and d == 50
-    also = a.also if a.also is not None else ("ref,ref2,10M,share,c5,pbmc" if default_main else "none")
+    also = (a.also if a.also is not None else ("ref,ref2,10M,share,c5,pbmc" if default_main else "none")) if a.full else "none"
     if world == 1 and also != "none":
         # extra legs of this invocation (never part of `value`): each one is a full run to convergence from HBM-resident inputs
         del obj

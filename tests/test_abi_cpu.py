@@ -349,26 +349,56 @@ def test_r_companion_package_assembles_and_registers_under_its_own_name(tmp_path
     assert called and called <= registered, sorted(called - registered)
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/R/ui.R"), reason="the reference package is not on this machine")
+REF_PACKAGE_FACTS = os.path.join(ROOT, "tests", "golden", "ref_package_facts.json")
+
+
+def ref_package_facts(pkg):
+    """What the test below needs to know of the reference package at `pkg`, as data and without its text: length and SHA-256 of every line
+    of R/ui.R, the routines src/RcppExports.cpp registers, and which of them R/utils.R calls (tools/make_ref_package_facts.py writes
+    tests/golden/ref_package_facts.json from it)."""
+    import hashlib
+    ui = open(os.path.join(pkg, "R", "ui.R")).read().split("\n")
+    routines = sorted(set(re.findall(r'\{"(_harmony_\w+)", \(DL_FUNC\)', open(os.path.join(pkg, "src", "RcppExports.cpp")).read())))
+    utils = open(os.path.join(pkg, "R", "utils.R")).read()
+    return {"ui_R_line_length": [len(l) for l in ui], "ui_R_line_sha256": [hashlib.sha256(l.encode()).hexdigest() for l in ui],
+            "registered_routines": routines,
+            "utils_R_calls": sorted(r[len("_harmony_"):] for r in routines if re.search(r"\b%s\(" % r[len("_harmony_"):], utils))}
+
+
 def test_the_one_line_edit_applies_to_the_reference_package(tmp_path):
-    """INTEGRATION.md's claim, executed on the reference's own file: r/ui_R_269.sed changes exactly ONE line of R/ui.R -- line 269,
+    """INTEGRATION.md's claim, checked against the reference's own file: r/ui_R_269.sed changes exactly ONE line of R/ui.R -- line 269,
     `harmonyObj <- new(harmony)` -- and leaves the reference's engine as the fallback.  And the reason the companion package is the
     recommended route: the reference's DLL registers three more routines than the module (src/RcppExports.cpp:60-62), one of which
-    (scaleRows_dgc) its own R code calls (R/utils.R:93) -- a glue that REPLACED that DLL's registration would break them."""
+    (scaleRows_dgc) its own R code calls (R/utils.R:93) -- a glue that REPLACED that DLL's registration would break them.
+    The package is read through tests/golden/ref_package_facts.json (line lengths and digests, no text); where the package itself is on disk,
+    the fixture must still describe it.  The sed pattern matches exactly the lines `<spaces>harmonyObj <- new(harmony)<spaces>`: every such
+    line of each recorded length is tried against the digests, so no other line of the file can be one."""
+    import hashlib
+    import json
     import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    ref = open("/root/reference/R/ui.R").read().split("\n")
+    from oracle import ref as oref
+    facts = json.load(open(REF_PACKAGE_FACTS))
+    pkg = os.path.dirname(oref._REF_SRC)
+    if os.path.exists(os.path.join(pkg, "R", "ui.R")):
+        assert ref_package_facts(pkg) == facts
+    stmt = "harmonyObj <- new(harmony)"
+    found = {}
+    for i, (n, h) in enumerate(zip(facts["ui_R_line_length"], facts["ui_R_line_sha256"])):
+        for lead in range(n - len(stmt) + 1):
+            line = " " * lead + stmt + " " * (n - len(stmt) - lead)
+            if hashlib.sha256(line.encode()).hexdigest() == h:
+                found[i + 1] = line
+    assert list(found) == [269], sorted(found)
+    old = [found[269], "harmonyObj$setup(", "    " + stmt + "  # not alone on its line"]
     work = tmp_path / "ui.R"
-    work.write_text("\n".join(ref))
-    assert subprocess.run(["sed", "-i", "-f", os.path.join(root, "r", "ui_R_269.sed"), str(work)]).returncode == 0
+    work.write_text("\n".join(old))
+    assert subprocess.run(["sed", "-i", "-f", os.path.join(ROOT, "r", "ui_R_269.sed"), str(work)]).returncode == 0
     new = work.read_text().split("\n")
-    diff = [i + 1 for i, (a, b) in enumerate(zip(ref, new)) if a != b]
-    assert len(ref) == len(new) and diff == [269]
-    assert ref[268].strip() == "harmonyObj <- new(harmony)"
-    assert "harmonymi355x::new_harmony_mi355x()" in new[268] and new[268].rstrip().endswith("else new(harmony)")
-    exports = open("/root/reference/src/RcppExports.cpp").read()
-    assert all(("_harmony_" + f) in exports for f in ("kmeans_centers", "scaleRows_dgc", "find_lambda_cpp"))
-    assert "scaleRows_dgc(" in open("/root/reference/R/utils.R").read()
+    assert len(new) == len(old) and new[1:] == old[1:] and new[0] != old[0]
+    assert new[0].startswith(found[269][:len(found[269]) - len(found[269].lstrip())] + "harmonyObj <- if (")
+    assert "harmonymi355x::new_harmony_mi355x()" in new[0] and new[0].rstrip().endswith("else new(harmony)")
+    assert {"_harmony_" + f for f in ("kmeans_centers", "scaleRows_dgc", "find_lambda_cpp")} <= set(facts["registered_routines"])
+    assert "scaleRows_dgc" in facts["utils_R_calls"]
 
 
 def test_methods_called_out_of_order_fail_cleanly():

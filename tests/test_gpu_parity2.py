@@ -975,7 +975,7 @@ def test_bench_two_ranks_default_is_configs3_strong_scaling():
     import subprocess
     import sys
     env = dict(os.environ, HMX_BENCH_PREROLL="0")
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "1", "--warmup", "0", "--no-e2e"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "1", "--warmup", "0", "--full", "--no-e2e"],
                        capture_output=True, text=True, timeout=1400, stdin=subprocess.DEVNULL, cwd=ROOT, env=env)
     assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-3000:])
     line = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])

@@ -5,8 +5,10 @@ object) over the C ABI in include/harmony_mi355x.h.  All numerics run in hand-wr
 (harmony_amd/csrc); there is no CPU fallback.
 """
 from .harmony_obj import Harmony, HarmonyError
+from .mapping import HarmonyReference, map_query
 from .options import harmony_options
 from .ui import RunHarmony, prepare_setup_args
 from .utils import harmonize
 
-__all__ = ["RunHarmony", "harmony_options", "Harmony", "HarmonyError", "harmonize", "prepare_setup_args"]
+__all__ = ["RunHarmony", "harmony_options", "Harmony", "HarmonyError", "harmonize", "prepare_setup_args", "map_query",
+           "HarmonyReference"]

@@ -28,6 +28,8 @@ SIGNATURES = {
                                _dp, _dp, C.c_int32, C.c_double, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_double,
                                _ip, C.c_int32, C.c_double, C.c_int32]),
     "hmx_restart": (C.c_int, [C.c_void_p]),
+    "hmx_map_query": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32, _ip, _ip, C.c_int32, _ip, C.c_int32,
+                                _dp, C.c_int32, C.c_double, C.c_double, _dp, _dp, _dp, C.c_int32]),
     "hmx_init_cluster": (C.c_int, [C.c_void_p, _dp]),
     "hmx_kmeans_centers": (C.c_int, [C.c_void_p, _dp]),
     "hmx_cluster": (C.c_int, [C.c_void_p]),

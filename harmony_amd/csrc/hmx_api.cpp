@@ -171,7 +171,7 @@ float hmx_u01(uint64_t seed, uint64_t stream, uint64_t idx) {
 int hmx_set_shard(hmx_ctx* ctx, int32_t rank, int32_t world, int64_t global_offset, int64_t N_global,
                   hmx_allreduce_fn fn, void* user) {
   if (!ctx) return HMX_ERR_ARG;
-  if (ctx->ran_setup) return fail(ctx, HMX_ERR_STATE, "hmx_set_shard must precede hmx_setup");
+  if (ctx->ran_setup || ctx->query_done) return fail(ctx, HMX_ERR_STATE, "hmx_set_shard must precede hmx_setup");
   if (world < 1 || rank < 0 || rank >= world) return fail(ctx, HMX_ERR_ARG, "bad shard description");
   if (world > 1 && !fn && !ctx->comm) return fail(ctx, HMX_ERR_ARG, "a sharded handle needs hmx_comm_init or an all-reduce hook");
   ctx->rank = rank; ctx->world = world; ctx->goff = global_offset; ctx->N_global = N_global; ctx->ar = fn; ctx->ar_user = user;
@@ -222,6 +222,7 @@ int hmx_comm_allreduce_host(hmx_ctx* ctx, double* inout, int32_t count, int32_t 
 }
 #include "hmx_api_p2p.inc"
 #include "hmx_api_setup.inc"
+#include "hmx_api_query.inc"
 int hmx_restart(hmx_ctx* ctx) {
   if (!ctx || !ctx->ran_setup) return ctx ? fail(ctx, HMX_ERR_STATE, "setup first") : HMX_ERR_ARG;
   HIPCHK(hipSetDevice(ctx->device));

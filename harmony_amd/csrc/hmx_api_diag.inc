@@ -207,8 +207,24 @@ int64_t hmx_get(hmx_ctx* ctx, const char* field, double* out, int64_t cap) {
   if (f == "objective_kmeans_cross") return vec(ctx->obj_cross);
   if (f == "objective_harmony") return vec(ctx->obj_harmony);
   if (f == "kmeans_rounds") return vec(ctx->kmeans_rounds);
+  if (ctx->query_done && (f == "Z_corr" || f == "Z_orig" || f == "R")) return hmx_get_matrix(ctx, field, out, HMX_F64, HMX_HOST, cap);
   if (!ctx->ran_setup) return -1;
   if (hipSetDevice(ctx->device) != hipSuccess) return -1;
+  if (f == "ref_Nr" || f == "ref_C") {       // reference summary for hmx_map_query, from the current R and Z_corr (sharded: collective)
+    if (ctx->ran_init && !ctx->R_valid) { ctx->err = "R is not available: the clustering call that would have stored it did not complete"; return -1; }
+    if (sync_solve_results(ctx)) return -1;
+    const int K = ctx->K, d = ctx->d;
+    const int64_t cnt = f == "ref_Nr" ? K : (int64_t)K * d;
+    if (!out) return cnt;
+    std::vector<double> res;
+    if (ref_summary(ctx, res)) return -1;
+    std::vector<double> v((size_t)cnt);
+    for (int k = 0; k < K; k++) {
+      if (f == "ref_Nr") v[k] = res[(size_t)k * (d + 1) + d];
+      else for (int j = 0; j < d; j++) v[k + (size_t)K * j] = res[(size_t)k * (d + 1) + j];
+    }
+    return vec(v);
+  }
   if (f == "seq:mismatch" || f == "seq:residual") {      // last scans of the restarted sequential sums: segment starts that still moved / the largest move relative to its chain's largest start
     if (!ctx->sq_mismatch) return scalar(0.0);
     bool dummy = false;
@@ -256,7 +272,7 @@ int64_t hmx_get(hmx_ctx* ctx, const char* field, double* out, int64_t cap) {
 // R seam; float and/or a device pointer avoid the fp64 blow-up and the PCIe trip for hosts that keep working on the GPU.
 // Host destinations are filled slab by slab through two HBM staging buffers (conversion of slab s+1 overlaps the copy of slab s).
 int64_t hmx_get_matrix(hmx_ctx* ctx, const char* field, void* out, int32_t dtype, int32_t location, int64_t cap) {
-  if (!ctx || !field || !ctx->ran_setup) return -1;
+  if (!ctx || !field || !(ctx->ran_setup || ctx->query_done)) return -1;
   const std::string f(field);
   if (f != "Z_corr" && f != "Z_orig" && f != "R") { ctx->err = "hmx_get_matrix: unknown field " + f; return -1; }
   if ((dtype != HMX_F64 && dtype != HMX_F32) || (location != HMX_HOST && location != HMX_DEVICE)) { ctx->err = "bad dtype / location"; return -1; }
@@ -267,6 +283,13 @@ int64_t hmx_get_matrix(hmx_ctx* ctx, const char* field, void* out, int32_t dtype
   const int64_t cnt = ctx->N * w;
   if (!out || cap < cnt) return cnt;
   const float* src = (f == "R") ? ctx->D.R : (f == "Z_corr" ? ctx->D.Zc : ctx->D.Zo);
+  // a mapped query keeps no R: its rows are recomputed from Z_orig into a buffer that lives for this call only
+  struct TmpR { float* p = nullptr; ~TmpR() { if (p) (void)hipFree(p); } } tmpR;
+  if (ctx->query_done && f == "R") {
+    if (hipMalloc((void**)&tmpR.p, sizeof(float) * (size_t)cnt) != hipSuccess) { (void)hipGetLastError(); ctx->err = "out of device memory for R"; return -1; }
+    if (query_R_rows(ctx, tmpR.p)) return -1;
+    src = tmpR.p;
+  }
   const int ws = (f == "R") ? w : ctx->D.zs;
   const int f32 = dtype == HMX_F32;
   const size_t esz = f32 ? 4 : 8;

@@ -256,6 +256,9 @@ struct hmx_ctx {
   // the sort-free form of the batched shuffle (k_shuf_*): position -> (cell, rank) per order set, the blocks of the round behind a batch,
   // the (block, bin, part) count matrix
   bool shuf_inv = false; int2* posr[4] = {}; int* shuf_partcnt[4] = {}; int* shuf_binacc[4] = {}; int64_t injected_round = -1;   // (injected_round: the round whose order the host provided -- its D.blk came with it)
+  // ---- query mapping (hmx_map_query): a handle that mapped a query serves Z_corr / Z_orig / R and nothing else
+  bool query_done = false;
+  QueryDev qd{};            // the query's device tables (rows in D.Zo / D.Zc, internal order in D.perm / D.invperm)
   std::string err, warn, warn_ret;
 };
 

@@ -1,4 +1,139 @@
 // hmx_api_setup.inc -- part of hmx_api.cpp (included there, ONE translation unit): hmx_setup / hmx_setup_ex (src/harmony.cpp:29-128): ingest, level codes, combination sort, HBM layout, launch shapes
+// ---- pieces shared by hmx_setup_ex and hmx_map_query ----------------------------------------------------------------------------
+// per-covariate level codes from the C-hot CSC design (src/harmony.cpp:49-65, R/ui.R:210-213): codes[c * N + i] = level of cell i in covariate c
+static int phi_codes(hmx_ctx* ctx, int64_t N, const int32_t* phi_i, const int32_t* phi_p, const double* phi_x, int32_t B, int32_t C,
+                     std::vector<int>& codes) {
+  codes.assign((size_t)C * N, 0);
+  for (int64_t i = 0; i < N; i++) {
+    if (phi_p[i + 1] - phi_p[i] != C) return fail(ctx, HMX_ERR_PHI, "Phi column does not hold exactly one level per covariate");
+    for (int c = 0; c < C; c++) {
+      const int b = phi_i[phi_p[i] + c];
+      if (b < 0 || b >= B || b >= ctx->cov_bounds[c] || (c > 0 && b < ctx->cov_bounds[c - 1]))
+        return fail(ctx, HMX_ERR_PHI, "Phi rows are not grouped by covariate");
+      if (phi_x && phi_x[phi_p[i] + c] != 1.0) return fail(ctx, HMX_ERR_PHI, "Phi must be a 0/1 design");
+      codes[(size_t)c * N + i] = b;
+    }
+  }
+  return 0;
+}
+// level combinations: dense mixed-radix key of every cell and the cells per key (identical on every rank)
+static int combo_keys(hmx_ctx* ctx, int64_t N, int32_t C, const std::vector<int>& codes, std::vector<int>& key, std::vector<long long>& present) {
+  double dense = 1; for (int c = 0; c < C; c++) dense *= ctx->B_vec[c];
+  if (dense > 16777216.0) return fail(ctx, HMX_ERR_LIMIT, "product of covariate level counts exceeds 2^24");
+  present.assign((size_t)dense, 0);
+  key.assign((size_t)N, 0);
+  for (int64_t i = 0; i < N; i++) {
+    int64_t kk = 0, mul = 1;
+    for (int c = 0; c < C; c++) { kk += mul * (codes[(size_t)c * N + i] - (c ? ctx->cov_bounds[c - 1] : 0)); mul *= ctx->B_vec[c]; }
+    key[i] = (int)kk; present[(size_t)kk]++;
+  }
+  return 0;
+}
+// compact combination ids (ctx->Q, ctx->qlev) and the internal order: cells sorted (stably) by combination (ctx->perm, invperm,
+// start[q] = first cell of combination q, combo_sorted = combination of every internal position)
+static void combo_order(hmx_ctx* ctx, int64_t N, int32_t C, const std::vector<long long>& present, const std::vector<int>& key,
+                        std::vector<int>& start, std::vector<int>& invperm, std::vector<int>& combo_sorted) {
+  const int64_t P = (int64_t)present.size();
+  std::vector<int> qid((size_t)P, -1);
+  ctx->Q = 0; ctx->qlev.clear();
+  for (int64_t kk = 0; kk < P; kk++) if (present[(size_t)kk] > 0) {
+    qid[(size_t)kk] = ctx->Q++;
+    int64_t rem = kk;
+    for (int c = 0; c < C; c++) { ctx->qlev.push_back((int)(rem % ctx->B_vec[c]) + (c ? ctx->cov_bounds[c - 1] : 0)); rem /= ctx->B_vec[c]; }
+  }
+  const int Q = ctx->Q;
+  std::vector<int> combo_of((size_t)N);
+  start.assign((size_t)Q + 1, 0); invperm.assign((size_t)N, 0); combo_sorted.assign((size_t)N, 0);
+  for (int64_t i = 0; i < N; i++) { combo_of[i] = qid[(size_t)key[i]]; start[(size_t)combo_of[i] + 1]++; }
+  for (int q = 0; q < Q; q++) start[q + 1] += start[q];
+  ctx->perm.assign((size_t)N, 0);
+  { std::vector<int> cur(start.begin(), start.end() - 1);
+    for (int64_t i = 0; i < N; i++) { const int p = cur[combo_of[i]]++; ctx->perm[p] = (int)i; invperm[i] = p; combo_sorted[p] = combo_of[i]; } }
+}
+// Z: d x N (cell-major) -> ctx->D.Zo (fp32 rows in internal order through ctx->D.invperm, stride D.zs); hmx_get("timer:ingest_Z")
+static int ingest_Z(hmx_ctx* ctx, const void* Z, int32_t z_dtype, int32_t z_location, int64_t N, int32_t d) {
+  Dev& D = ctx->D;
+  // Z: d x N (cell-major), double (the R seam, conv_to :41) or float, on the host or already in HBM -> fp32 rows in internal
+  // order.  Host input goes through two HBM staging slabs: the copy of slab s+1 (copy stream) overlaps the conversion of slab s.
+  if (z_location != HMX_DEVICE && xfer_mode() == 2) (void)xfer_ring(ctx->device).ensure();    // (once per process: not part of a matrix's transfer time)
+  // (the buffers' first touch by the clears above is allocate_buffers' time, and the first launch of a library kernel in a process loads the
+  //  code object -- tens of ms once per process --: neither is the ingest's)
+  l_copy(ctx->L, D.Zo, D.Zo, 0); KCHK();
+  HIPCHK(hipStreamSynchronize(ctx->L.stream));
+  {
+    const double t_in = now_ms();
+    const int f32 = z_dtype == HMX_F32;
+    const size_t esz = f32 ? 4 : 8;
+    if (z_location == HMX_DEVICE) {
+      l_convert_in(ctx->L, Z, f32, D.Zo, D.invperm, (int)N, d, D.zs); KCHK();
+      HIPCHK(hipStreamSynchronize(ctx->L.stream));
+    } else if (xfer_mode() == 2 && xfer_ring(ctx->device).ensure()) {
+      // ring of page-locked slots: host threads fill slot b while the DMA engine drains the earlier ones and the conversion kernel
+      // consumes what has landed (two HBM staging slabs)
+      XferRing& ring = xfer_ring(ctx->device);
+      std::lock_guard<std::mutex> ring_lock(ring.mu);
+      XferPool pool; pool.start(xfer_threads());
+      const int64_t slab = std::max<int64_t>(1, (int64_t)XferRing::SLOT / ((int64_t)esz * d));
+      hipStream_t cs = ring.cs;
+      hipEvent_t* copied = ring.ev_a; hipEvent_t* used = ring.ev_b; hipEvent_t* left = ring.ev_slot;   // left[b]: slot b's bytes have left for the device
+      ctx->timers["ingest_pinned"] = 2.0;
+      hipError_t e = hipSuccess;
+      int it = 0;
+      for (int64_t s0 = 0; s0 < N && e == hipSuccess; s0 += slab, it++) {
+        const int64_t cnt = std::min<int64_t>(slab, N - s0);
+        const size_t nbytes = (size_t)cnt * d * esz;
+        const int b = it & 1, rb = it % XferRing::NB;
+        if (it >= XferRing::NB) e = hipEventSynchronize(left[rb]);
+        if (e != hipSuccess) break;
+        pool.copy(ring.slot[rb], (const char*)Z + (size_t)s0 * d * esz, nbytes);
+        if (it >= 2) e = hipStreamWaitEvent(cs, used[b], 0);           // the slab's previous conversion has read it
+        if (e == hipSuccess) e = hipMemcpyAsync(ring.stage[b], ring.slot[rb], nbytes, hipMemcpyHostToDevice, cs);
+        if (e == hipSuccess) e = hipEventRecord(left[rb], cs);
+        if (e == hipSuccess) e = hipEventRecord(copied[b], cs);
+        if (e == hipSuccess) e = hipStreamWaitEvent(ctx->L.stream, copied[b], 0);
+        if (e == hipSuccess) { l_convert_in(ctx->L, ring.stage[b], f32, D.Zo, D.invperm + s0, (int)cnt, d, D.zs); e = hipGetLastError(); }
+        if (e == hipSuccess) e = hipEventRecord(used[b], ctx->L.stream);
+      }
+      if (e == hipSuccess) e = hipStreamSynchronize(ctx->L.stream);
+      (void)hipStreamSynchronize(cs);
+      if (e != hipSuccess) return fail(ctx, HMX_ERR_DEVICE, hipGetErrorString(e));
+    } else {
+      const int64_t slab = std::max<int64_t>(1, (int64_t)(128ll << 20) / ((int64_t)esz * d));
+      const int64_t scnt = std::min<int64_t>(slab, N);
+      void* stage[2] = {nullptr, nullptr}; hipStream_t cs = nullptr; hipEvent_t copied[2] = {nullptr, nullptr}, used[2] = {nullptr, nullptr};
+      // The caller's matrix is pageable (R's heap): page-lock it for the duration of the ingest, so that the slab copies are real DMA
+      // at PCIe speed instead of the runtime's staged pageable path (HMX_PIN=0 leaves it pageable; a failed registration is not an error).
+      const bool pinned = xfer_mode() >= 1 && hipHostRegister(const_cast<void*>(Z), (size_t)N * d * esz, hipHostRegisterDefault) == hipSuccess;
+      if (!pinned) (void)hipGetLastError();
+      ctx->timers["ingest_pinned"] = pinned ? 1.0 : 0.0;
+      hipError_t e = hipStreamCreateWithFlags(&cs, hipStreamNonBlocking);
+      for (int i = 0; i < 2 && e == hipSuccess; i++) {
+        e = hipMalloc(&stage[i], (size_t)scnt * d * esz);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&copied[i], hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&used[i], hipEventDisableTiming);
+      }
+      int it = 0;
+      for (int64_t s0 = 0; s0 < N && e == hipSuccess; s0 += slab, it++) {
+        const int64_t cnt = std::min<int64_t>(slab, N - s0);
+        const int b = it & 1;
+        if (it >= 2) e = hipStreamWaitEvent(cs, used[b], 0);           // the slab's previous conversion has read it
+        if (e == hipSuccess) e = hipMemcpyAsync(stage[b], (const char*)Z + (size_t)s0 * d * esz, (size_t)cnt * d * esz, hipMemcpyHostToDevice, cs);
+        if (e == hipSuccess) e = hipEventRecord(copied[b], cs);
+        if (e == hipSuccess) e = hipStreamWaitEvent(ctx->L.stream, copied[b], 0);
+        if (e == hipSuccess) { l_convert_in(ctx->L, stage[b], f32, D.Zo, D.invperm + s0, (int)cnt, d, D.zs); e = hipGetLastError(); }
+        if (e == hipSuccess) e = hipEventRecord(used[b], ctx->L.stream);
+      }
+      if (e == hipSuccess) e = hipStreamSynchronize(ctx->L.stream);
+      for (int i = 0; i < 2; i++) { if (stage[i]) (void)hipFree(stage[i]); if (copied[i]) (void)hipEventDestroy(copied[i]); if (used[i]) (void)hipEventDestroy(used[i]); }
+      if (cs) (void)hipStreamDestroy(cs);
+      if (pinned) (void)hipHostUnregister(const_cast<void*>(Z));
+      if (e != hipSuccess) return fail(ctx, HMX_ERR_DEVICE, hipGetErrorString(e));
+    }
+    ctx->timers["ingest_Z"] = now_ms() - t_in;
+  }
+  return 0;
+}
+
 // ---- setup (src/harmony.cpp:29-128) -------------------------------------------------------------------
 int hmx_setup(hmx_ctx* ctx, const double* Z, int64_t N, int32_t d, const int32_t* phi_i, const int32_t* phi_p,
               const double* phi_x, int32_t B, const double* sigma, const double* theta, const double* lambda,
@@ -14,6 +149,7 @@ int hmx_setup_ex(hmx_ctx* ctx, const void* Z, int32_t z_dtype, int32_t z_locatio
                  double epsilon_harmony, int32_t K, double block_size, const int32_t* B_vec, int32_t C, double cutoff,
                  int32_t verbose) {
   if (!ctx) return HMX_ERR_ARG;
+  if (ctx->query_done) return fail(ctx, HMX_ERR_STATE, "this handle mapped a query: create a new handle for a fit");
   if ((z_dtype != HMX_F64 && z_dtype != HMX_F32) || (z_location != HMX_HOST && z_location != HMX_DEVICE))
     return fail(ctx, HMX_ERR_ARG, "bad dtype / location of Z");
   ctx->err.clear(); ctx->warn.clear();
@@ -62,28 +198,11 @@ int hmx_setup_ex(hmx_ctx* ctx, const void* Z, int32_t z_dtype, int32_t z_locatio
   if (ctx->nb < 1) ctx->nb = 1;
 
   // ---- per-covariate level codes from the C-hot CSC design (src/harmony.cpp:49-65, R/ui.R:210-213)
-  std::vector<int> codes((size_t)C * N);
-  for (int64_t i = 0; i < N; i++) {
-    if (phi_p[i + 1] - phi_p[i] != C) return fail(ctx, HMX_ERR_PHI, "Phi column does not hold exactly one level per covariate");
-    for (int c = 0; c < C; c++) {
-      const int b = phi_i[phi_p[i] + c];
-      if (b < 0 || b >= B || b >= ctx->cov_bounds[c] || (c > 0 && b < ctx->cov_bounds[c - 1]))
-        return fail(ctx, HMX_ERR_PHI, "Phi rows are not grouped by covariate");
-      if (phi_x && phi_x[phi_p[i] + c] != 1.0) return fail(ctx, HMX_ERR_PHI, "Phi must be a 0/1 design");
-      codes[(size_t)c * N + i] = b;
-    }
-  }
-  // ---- level combinations: dense mixed-radix key -> compact id (identical on every rank)
-  double dense = 1; for (int c = 0; c < C; c++) dense *= ctx->B_vec[c];
-  if (dense > 16777216.0) return fail(ctx, HMX_ERR_LIMIT, "product of covariate level counts exceeds 2^24");
-  const int64_t P = (int64_t)dense;
-  std::vector<long long> present((size_t)P, 0);
-  std::vector<int> key((size_t)N);
-  for (int64_t i = 0; i < N; i++) {
-    int64_t kk = 0, mul = 1;
-    for (int c = 0; c < C; c++) { kk += mul * (codes[(size_t)c * N + i] - (c ? ctx->cov_bounds[c - 1] : 0)); mul *= ctx->B_vec[c]; }
-    key[i] = (int)kk; present[(size_t)kk]++;
-  }
+  std::vector<int> codes, key;
+  std::vector<long long> present;
+  CHK(phi_codes(ctx, N, phi_i, phi_p, phi_x, B, C, codes));
+  CHK(combo_keys(ctx, N, C, codes, key, present));
+  const int64_t P = (int64_t)present.size();
   // global level sizes N_b and global presence (one all-reduce each when sharded)
   std::vector<long long> nbcount((size_t)B, 0);
   for (int c = 0; c < C; c++) for (int64_t i = 0; i < N; i++) nbcount[codes[(size_t)c * N + i]]++;
@@ -99,23 +218,11 @@ int hmx_setup_ex(hmx_ctx* ctx, const void* Z, int32_t z_dtype, int32_t z_locatio
     std::copy(tmp.begin(), tmp.begin() + P, present.begin());
     std::copy(tmp.begin() + P, tmp.end(), nbcount.begin());
   }
-  std::vector<int> qid((size_t)P, -1);
-  ctx->Q = 0; ctx->qlev.clear();
-  for (int64_t kk = 0; kk < P; kk++) if (present[(size_t)kk] > 0) {
-    qid[(size_t)kk] = ctx->Q++;
-    int64_t rem = kk;
-    for (int c = 0; c < C; c++) { ctx->qlev.push_back((int)(rem % ctx->B_vec[c]) + (c ? ctx->cov_bounds[c - 1] : 0)); rem /= ctx->B_vec[c]; }
-  }
+  std::vector<int> start, invperm, combo_sorted;
+  combo_order(ctx, N, C, present, key, start, invperm, combo_sorted);
   const int Q = ctx->Q;
   ctx->sizes.resize(B); ctx->Pr_b.resize(B);
   for (int b = 0; b < B; b++) { ctx->sizes[b] = (float)nbcount[b]; ctx->Pr_b[b] = ctx->sizes[b] / (float)ctx->N_global; }  // :67
-  // ---- internal order: cells sorted (stably) by combination
-  std::vector<int> combo_of((size_t)N), start((size_t)Q + 1, 0), invperm((size_t)N), combo_sorted((size_t)N);
-  for (int64_t i = 0; i < N; i++) { combo_of[i] = qid[(size_t)key[i]]; start[(size_t)combo_of[i] + 1]++; }
-  for (int q = 0; q < Q; q++) start[q + 1] += start[q];
-  ctx->perm.assign((size_t)N, 0);
-  { std::vector<int> cur(start.begin(), start.end() - 1);
-    for (int64_t i = 0; i < N; i++) { const int p = cur[combo_of[i]]++; ctx->perm[p] = (int)i; invperm[i] = p; combo_sorted[p] = combo_of[i]; } }
   std::vector<Item> items, aitems, titems;
   for (int q = 0; q < Q; q++) {
     for (int s = start[q]; s < start[q + 1]; s += ITEM_CELLS) items.push_back({q, s, std::min(ITEM_CELLS, start[q + 1] - s)});
@@ -307,84 +414,7 @@ int hmx_setup_ex(hmx_ctx* ctx, const void* Z, int32_t z_dtype, int32_t z_locatio
   HIPCHK(hipMemsetAsync(D.Zo, 0, sizeof(float) * (size_t)N * D.zs, ctx->L.stream));
   HIPCHK(hipMemsetAsync(D.Zc, 0, sizeof(float) * (size_t)N * D.zs, ctx->L.stream));
   HIPCHK(hipMemsetAsync(D.Wq, 0, sizeof(float) * (size_t)Q * K * d, ctx->L.stream));
-  // Z: d x N (cell-major), double (the R seam, conv_to :41) or float, on the host or already in HBM -> fp32 rows in internal
-  // order.  Host input goes through two HBM staging slabs: the copy of slab s+1 (copy stream) overlaps the conversion of slab s.
-  if (z_location != HMX_DEVICE && xfer_mode() == 2) (void)xfer_ring(ctx->device).ensure();    // (once per process: not part of a matrix's transfer time)
-  // (the buffers' first touch by the clears above is allocate_buffers' time, and the first launch of a library kernel in a process loads the
-  //  code object -- tens of ms once per process --: neither is the ingest's)
-  l_copy(ctx->L, D.Zo, D.Zo, 0); KCHK();
-  HIPCHK(hipStreamSynchronize(ctx->L.stream));
-  {
-    const double t_in = now_ms();
-    const int f32 = z_dtype == HMX_F32;
-    const size_t esz = f32 ? 4 : 8;
-    if (z_location == HMX_DEVICE) {
-      l_convert_in(ctx->L, Z, f32, D.Zo, D.invperm, (int)N, d, D.zs); KCHK();
-      HIPCHK(hipStreamSynchronize(ctx->L.stream));
-    } else if (xfer_mode() == 2 && xfer_ring(ctx->device).ensure()) {
-      // ring of page-locked slots: host threads fill slot b while the DMA engine drains the earlier ones and the conversion kernel
-      // consumes what has landed (two HBM staging slabs)
-      XferRing& ring = xfer_ring(ctx->device);
-      std::lock_guard<std::mutex> ring_lock(ring.mu);
-      XferPool pool; pool.start(xfer_threads());
-      const int64_t slab = std::max<int64_t>(1, (int64_t)XferRing::SLOT / ((int64_t)esz * d));
-      hipStream_t cs = ring.cs;
-      hipEvent_t* copied = ring.ev_a; hipEvent_t* used = ring.ev_b; hipEvent_t* left = ring.ev_slot;   // left[b]: slot b's bytes have left for the device
-      ctx->timers["ingest_pinned"] = 2.0;
-      hipError_t e = hipSuccess;
-      int it = 0;
-      for (int64_t s0 = 0; s0 < N && e == hipSuccess; s0 += slab, it++) {
-        const int64_t cnt = std::min<int64_t>(slab, N - s0);
-        const size_t nbytes = (size_t)cnt * d * esz;
-        const int b = it & 1, rb = it % XferRing::NB;
-        if (it >= XferRing::NB) e = hipEventSynchronize(left[rb]);
-        if (e != hipSuccess) break;
-        pool.copy(ring.slot[rb], (const char*)Z + (size_t)s0 * d * esz, nbytes);
-        if (it >= 2) e = hipStreamWaitEvent(cs, used[b], 0);           // the slab's previous conversion has read it
-        if (e == hipSuccess) e = hipMemcpyAsync(ring.stage[b], ring.slot[rb], nbytes, hipMemcpyHostToDevice, cs);
-        if (e == hipSuccess) e = hipEventRecord(left[rb], cs);
-        if (e == hipSuccess) e = hipEventRecord(copied[b], cs);
-        if (e == hipSuccess) e = hipStreamWaitEvent(ctx->L.stream, copied[b], 0);
-        if (e == hipSuccess) { l_convert_in(ctx->L, ring.stage[b], f32, D.Zo, D.invperm + s0, (int)cnt, d, D.zs); e = hipGetLastError(); }
-        if (e == hipSuccess) e = hipEventRecord(used[b], ctx->L.stream);
-      }
-      if (e == hipSuccess) e = hipStreamSynchronize(ctx->L.stream);
-      (void)hipStreamSynchronize(cs);
-      if (e != hipSuccess) return fail(ctx, HMX_ERR_DEVICE, hipGetErrorString(e));
-    } else {
-      const int64_t slab = std::max<int64_t>(1, (int64_t)(128ll << 20) / ((int64_t)esz * d));
-      const int64_t scnt = std::min<int64_t>(slab, N);
-      void* stage[2] = {nullptr, nullptr}; hipStream_t cs = nullptr; hipEvent_t copied[2] = {nullptr, nullptr}, used[2] = {nullptr, nullptr};
-      // The caller's matrix is pageable (R's heap): page-lock it for the duration of the ingest, so that the slab copies are real DMA
-      // at PCIe speed instead of the runtime's staged pageable path (HMX_PIN=0 leaves it pageable; a failed registration is not an error).
-      const bool pinned = xfer_mode() >= 1 && hipHostRegister(const_cast<void*>(Z), (size_t)N * d * esz, hipHostRegisterDefault) == hipSuccess;
-      if (!pinned) (void)hipGetLastError();
-      ctx->timers["ingest_pinned"] = pinned ? 1.0 : 0.0;
-      hipError_t e = hipStreamCreateWithFlags(&cs, hipStreamNonBlocking);
-      for (int i = 0; i < 2 && e == hipSuccess; i++) {
-        e = hipMalloc(&stage[i], (size_t)scnt * d * esz);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&copied[i], hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&used[i], hipEventDisableTiming);
-      }
-      int it = 0;
-      for (int64_t s0 = 0; s0 < N && e == hipSuccess; s0 += slab, it++) {
-        const int64_t cnt = std::min<int64_t>(slab, N - s0);
-        const int b = it & 1;
-        if (it >= 2) e = hipStreamWaitEvent(cs, used[b], 0);           // the slab's previous conversion has read it
-        if (e == hipSuccess) e = hipMemcpyAsync(stage[b], (const char*)Z + (size_t)s0 * d * esz, (size_t)cnt * d * esz, hipMemcpyHostToDevice, cs);
-        if (e == hipSuccess) e = hipEventRecord(copied[b], cs);
-        if (e == hipSuccess) e = hipStreamWaitEvent(ctx->L.stream, copied[b], 0);
-        if (e == hipSuccess) { l_convert_in(ctx->L, stage[b], f32, D.Zo, D.invperm + s0, (int)cnt, d, D.zs); e = hipGetLastError(); }
-        if (e == hipSuccess) e = hipEventRecord(used[b], ctx->L.stream);
-      }
-      if (e == hipSuccess) e = hipStreamSynchronize(ctx->L.stream);
-      for (int i = 0; i < 2; i++) { if (stage[i]) (void)hipFree(stage[i]); if (copied[i]) (void)hipEventDestroy(copied[i]); if (used[i]) (void)hipEventDestroy(used[i]); }
-      if (cs) (void)hipStreamDestroy(cs);
-      if (pinned) (void)hipHostUnregister(const_cast<void*>(Z));
-      if (e != hipSuccess) return fail(ctx, HMX_ERR_DEVICE, hipGetErrorString(e));
-    }
-    ctx->timers["ingest_Z"] = now_ms() - t_in;
-  }
+  CHK(ingest_Z(ctx, Z, z_dtype, z_location, N, d));
   ctx->W.assign((size_t)(B + 1) * d, 0.f); ctx->W_rows = B + 1;  // allocate_buffers :127
   ctx->Y.assign((size_t)d * K, 0.f);
   { const char* e = getenv("HMX_FUSED_FOLD");

@@ -310,6 +310,24 @@ void l_lloyd_finish(const Launch& L, const Dev& D);
 void l_y_images(const Launch& L, const Dev& D, const double* rows, int normalise);
 size_t lds_bytes_y(const Dev& D);
 
+// ---- query mapping and reference summary (hmx_query.hip) -----------------------------------------------------------------------------
+struct QueryDev {
+  int n, d, K, zs, KP16;       // cells, PCs, clusters, row stride, K rounded up to 16
+  const float* Z;              // [n][zs] query rows (internal order)
+  const float* yhat;           // [KP16][zs] normalised reference centroids (rows >= K and pads 0)
+  const float* sig2;           // [K] 2 / sigma_k
+  const Item* chunks; int nchunks;   // contiguous cells of one combination each (the summary: of the whole handle)
+  int slice;                   // statistics entries per workgroup (blockIdx.y), <= QUERY_SLICE
+  double* part;                // [nchunks][K (d + 1)] partial sums of every chunk
+  const float* Zsum; const float* Rsum;   // summary: the fitted handle's Z_corr rows [n][zs] and R rows [n][K]
+  const float* Wq; int w_lds;  // [Q][K][d] correction table; staged in LDS by k_query_apply when it fits
+  float* out; float* Rout;     // [n][zs] Z_corr rows / [n][K] R rows (either may be nullptr)
+};
+constexpr int QUERY_SLICE = 6144;          // 48 KB of fp64 accumulators per workgroup
+void l_query_stats(const Launch& L, const QueryDev& Q, int summary);
+void l_query_fold(const Launch& L, const double* part, const int* qchunk, int nq, int total, double* out);
+void l_query_apply(const Launch& L, const QueryDev& Q);
+
 // ---- reference arithmetic: restarted sequential fp32 sums (hmx_seq.hip) ------------------------------------------------------------
 struct SeqSeg { int off; int cnt; };       // a segment of a chain: cells list[off .. off + cnt) (or the cells off .. off + cnt - 1 themselves)
 struct SeqChain { int seg0; int nseg; };   // the segments of one chain, in chain order

@@ -201,6 +201,43 @@ class Harmony(object):
             self.warnings.append(w)
             warnings.warn(w)
 
+    def reference_summary(self):
+        """The fitted state a query is mapped onto (hmx_get "ref_Nr" / "ref_C" / "sigma"): a HarmonyReference.  Collective on a sharded
+        handle: every rank calls it and gets the global summary."""
+        from .mapping import HarmonyReference
+        K, d = int(self.K), int(self.d)
+        return HarmonyReference(self._get("ref_Nr"), self._get("ref_C", (K, d)), self._get("sigma"))
+
+    def map_query(self, Zq, Phi, B_vec, lambda_vec, alpha, batch_proportion_cutoff, reference):
+        """hmx_map_query on this (fresh) handle.  Zq: d x Nq numpy array (float64 or float32) or a device buffer (d, Nq, dtype,
+        device_pointer) as for setup; Phi: (i, p, x, B) of the query's own design; reference: a HarmonyReference.  Afterwards getZcorr() /
+        getR() / getZorig() return the mapped query."""
+        z_loc = 0
+        if isinstance(Zq, tuple):
+            d, N, zdt, zptr = Zq
+            z_dtype = 1 if np.dtype(zdt) == np.float32 else 0
+            z_loc, zarg = 1, C.c_void_p(int(zptr))
+        else:
+            z_dtype = 1 if getattr(Zq, "dtype", None) == np.float32 else 0
+            Zq = np.asfortranarray(Zq, dtype=np.float32 if z_dtype else np.float64)
+            d, N = Zq.shape
+            zarg = C.c_void_p(Zq.ctypes.data)
+        phi_i, phi_p, _phi_x, B = Phi
+        phi_i = np.ascontiguousarray(phi_i, dtype=np.int32)
+        phi_p = np.ascontiguousarray(phi_p, dtype=np.int32)
+        lam = np.ascontiguousarray(np.atleast_1d(lambda_vec), dtype=np.float64)
+        B_vec = np.ascontiguousarray(np.atleast_1d(B_vec), dtype=np.int32)
+        Nr = np.ascontiguousarray(reference.Nr, dtype=np.float64)
+        Cr = np.asfortranarray(reference.C, dtype=np.float64)
+        sg = np.ascontiguousarray(reference.sigma, dtype=np.float64)
+        K = Nr.size
+        if Cr.shape != (K, d) or sg.size != K:
+            raise HarmonyError("reference summary shapes (%s, %s, %s) do not match d = %d" % (Nr.shape, Cr.shape, sg.shape, d))
+        st = self._lib.hmx_map_query(self._h, zarg, z_dtype, z_loc, int(N), int(d), _iptr(phi_i), _iptr(phi_p), int(B), _iptr(B_vec),
+                                     B_vec.size, _dptr(lam), lam.size, float(alpha), float(batch_proportion_cutoff), _dptr(Nr),
+                                     _dptr(Cr), _dptr(sg), int(K))
+        self._check(st, "map_query")
+
     def init_cluster_cpp(self, Y0=None):
         if Y0 is None:
             st = self._lib.hmx_init_cluster(self._h, None)

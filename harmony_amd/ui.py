@@ -47,6 +47,24 @@ def build_phi(factor_codes, n_levels):
     return phi_i, phi_p, None, int(np.sum(n_levels))
 
 
+def lambda_vector(lambda_, B_vec, verbose=False):
+    """The ridge penalty as the library takes it (R/ui.R:224-249): None -> [-1] (automatic estimation, alpha * E); a scalar -> 0 followed by
+    that value for every level; one value per covariate -> 0 followed by each covariate's value for each of its levels."""
+    if lambda_ is None:
+        if verbose:
+            _message("Using automatic lambda estimation")
+        return np.array([-1.0])
+    lam = np.atleast_1d(np.asarray(lambda_, dtype=float))
+    if not np.all(lam > 0):
+        raise ValueError("Provided lambdas must be positive")
+    if lam.size == 1:
+        return np.concatenate([[0.0], np.repeat(lam, int(np.sum(B_vec)))])
+    if lam.size != len(B_vec):
+        raise ValueError("You specified a lambda value for each covariate but the number of lambdas "
+                         "specified (%d) and the number of covariates (%d) mismatch." % (lam.size, len(B_vec)))
+    return np.concatenate([[0.0]] + [np.repeat(lam[b], B_vec[b]) for b in range(len(B_vec))])
+
+
 def prepare_setup_args(data_mat, meta_data, vars_use, theta=None, sigma=0.1, lambda_=None, nclust=None,
                        early_stop=True, verbose=False, options=None, N_b=None, levels=None):
     """Everything RunHarmony.default computes before `new(harmony)` (R/ui.R:133-258).
@@ -106,21 +124,7 @@ def prepare_setup_args(data_mat, meta_data, vars_use, theta=None, sigma=0.1, lam
     if N_b is None:
         N_b = np.concatenate([np.bincount(c, minlength=n) for c, n in zip(codes, n_levels)]).astype(float)
 
-    if lambda_ is None:  # R/ui.R:224-249
-        if verbose:
-            _message("Using automatic lambda estimation")
-        lambda_vec = np.array([-1.0])
-    else:
-        lam = np.atleast_1d(np.asarray(lambda_, dtype=float))
-        if not np.all(lam > 0):
-            raise ValueError("Provided lambdas must be positive")
-        if lam.size == 1:
-            lambda_vec = np.concatenate([[0.0], np.repeat(lam, int(B_vec.sum()))])
-        else:
-            if lam.size != len(vars_use):
-                raise ValueError("You specified a lambda value for each covariate but the number of lambdas "
-                                 "specified (%d) and the number of covariates (%d) mismatch." % (lam.size, len(vars_use)))
-            lambda_vec = np.concatenate([[0.0]] + [np.repeat(lam[b], B_vec[b]) for b in range(len(B_vec))])
+    lambda_vec = lambda_vector(lambda_, B_vec, verbose)
 
     theta_lv = np.concatenate([np.repeat(theta[b], B_vec[b]) for b in range(len(B_vec))])  # R/ui.R:254-255
     if tau > 0:  # R/ui.R:258; tau == 0 leaves theta unchanged (1 - exp(-Inf))

@@ -119,7 +119,11 @@ int hmx_compute_objective(hmx_ctx* ctx);
  * "objective_kmeans_cross" "objective_harmony" "kmeans_rounds" "N" "B" "K" "d" "alpha"
  * "max_iter_kmeans" "W_rows" (+ diagnostics: "subset_clusters" "skipped_clusters" "n_combos" "usig"
  * "upd_wps" "comm:calls" "comm:bytes" and "timer:<phase>" in ms).  Returns the number of doubles the field holds (call with
- * out == NULL to size), or -1 for an unknown field.  At most `cap` values are written. */
+ * out == NULL to size), or -1 for an unknown field.  At most `cap` values are written.
+ * Reference summary for hmx_map_query (no reference counterpart): "ref_Nr" (K values, Nr[k] = sum_i R[k,i]) and "ref_C" (K x d,
+ * Cref[k,:] = sum_i R[k,i] Z_corr[:,i]), summed on the device over the R and Z_corr that "R" / "Z_corr" return at that moment, in a fixed
+ * order (bit-reproducible).  -1 where "R" is not available.  On a sharded handle the sums are all-reduced over the ranks: every rank gets
+ * the global summary, and a call with out != NULL is a COLLECTIVE call (every rank, same order). */
 int64_t hmx_get(hmx_ctx* ctx, const char* field, double* out, int64_t cap);
 /* getZcorr / getZorig / getR (src/harmony.cpp:640-655) with a choice of element type (HMX_F64 = the R seam, HMX_F32) and
  * destination (HMX_HOST or HMX_DEVICE pointer); `cap` counts elements.  Host destinations are filled slab by slab
@@ -127,6 +131,22 @@ int64_t hmx_get(hmx_ctx* ctx, const char* field, double* out, int64_t cap);
  * into `out` (pageable, possibly never touched: R's allocMatrix) while the next slabs are on their way.
  * hmx_get(ctx, "Z_corr", ...) is this with (F64, HOST). */
 int64_t hmx_get_matrix(hmx_ctx* ctx, const char* field, void* out, int32_t dtype, int32_t location, int64_t cap);
+/* ---- query mapping (Symphony's mapQuery, Kang et al. 2021; no counterpart in the reference package) ----------------------
+ * Maps query cells Zq (d x Nq, the reference's PC space; z_dtype / z_location as for hmx_setup_ex) onto a fitted reference given by its
+ * summary: Nr[K], Cref (K x d, column-major) and sigma[K] (hmx_get "ref_Nr" / "ref_C" / "sigma" of the fitted handle).  The query's design
+ * phi_i / phi_p (B x Nq, C ones per column, rows grouped by covariate as for hmx_setup; all ones) has its own levels, independent of the
+ * reference's.  lambda: B+1 values (entry 0 unused) or the single value -1 = alpha * E.  Per cluster k the levels b with
+ * sum_{i in b} R[k,i] / N_b > batch_proportion_cutoff enter the regression (one kept level is enough); the intercept carries the reference's mass
+ * Nr[k] and centroid Cref[k,:] and is not removed.  Two passes over Zq on the device (R is never stored), K ridge solves in fp64.
+ * Called on a FRESH single-GPU handle (HMX_ERR_STATE after hmx_setup or a first mapping, HMX_ERR_ARG after hmx_set_shard); no 6-cell floor.
+ * Afterwards the handle serves "Z_corr" (the mapped query), "Z_orig", "R" (recomputed on request, not kept), "N", "d", "K", "B" and
+ * "timer:map_query" through hmx_get / hmx_get_matrix; every other method returns HMX_ERR_STATE.  Shapes and the design are checked before
+ * the device is touched (HMX_ERR_ARG / HMX_ERR_LIMIT / HMX_ERR_PHI); a system that does not factor returns HMX_ERR_SOLVE. */
+int hmx_map_query(hmx_ctx* ctx, const void* Zq, int32_t z_dtype, int32_t z_location, int64_t Nq, int32_t d,
+                  const int32_t* phi_i, const int32_t* phi_p, int32_t B, const int32_t* B_vec, int32_t C,
+                  const double* lambda, int32_t n_lambda, double alpha, double batch_proportion_cutoff,
+                  const double* Nr, const double* Cref, const double* sigma, int32_t K);
+
 /* writable fields: "max_iter_kmeans" (vignettes/detailedWalkthrough.Rmd:364), "seed",
  * "device" (before setup), "profile" (HIP-event timing of the update kernel, see "measurement"),
  * "rng" (0 counter-based generator | 1 R-compatible stream, see "randomness"),

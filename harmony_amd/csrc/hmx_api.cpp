@@ -283,7 +283,7 @@ int hmx_compute_objective(hmx_ctx* ctx) {  // src/harmony.cpp:158-170 on the cur
   Dev Ds = ctx->D;
   const bool stale = ctx->stale_dist && ctx->head_is_stale;
   if (stale) { Ds.Zc = ctx->Zc_head; Ds.Yt = ctx->Yt_head; Ds.obj_stale = 1; }          // the reference's stored dist_mat (:160)
-  l_head(ctx->L, Ds, 1); KCHK();
+  l_head(ctx->L, Ds); KCHK();
   l_obj_reduce(ctx->L, ctx->D); KCHK();
   CHK(allreduce(ctx, ctx->D.obj, 2, 1));
   CHK(objective_snapshot(ctx, stale ? &Ds : nullptr));     // (obj_arith re-derives the terms: from the same snapshot)

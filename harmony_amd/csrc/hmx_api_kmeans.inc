@@ -69,14 +69,10 @@ int kmeans_centers(hmx_ctx* ctx) {
   } else {
   // exponential race for every anchor in one pass (:24-34)
   CHK(h2d(ctx, D.seedmin, sentinel.data(), (size_t)K));
-  // the race on the matrix cores (k_tile mode 3) when the centroid image fits; else the cluster-lane VALU kernel
-  const bool seed_tile = D.tile_impl && (size_t)D.NQ * D.NS * 1024 <= 150 * 1024;
+  // the race on the matrix cores (k_tile mode 3)
   auto seed_probe = [&](const unsigned* excl, int nexcl) -> int {
-    if (seed_tile) {
-      ctx->D.seed_key = ctx->seed; ctx->D.seed_goff = (unsigned long long)ctx->goff; ctx->D.seed_excl = excl; ctx->D.seed_nexcl = nexcl;
-      l_tile_static(ctx->L, ctx->D, 3);
-    } else l_seed_probe(ctx->L, D, ctx->seed, (uint64_t)ctx->goff, excl, nexcl);
-    KCHK();
+    ctx->D.seed_key = ctx->seed; ctx->D.seed_goff = (unsigned long long)ctx->goff; ctx->D.seed_excl = excl; ctx->D.seed_nexcl = nexcl;
+    l_tile_static(ctx->L, ctx->D, 3); KCHK();
     return 0;
   };
   CHK(seed_probe(nullptr, 0));
@@ -104,7 +100,8 @@ int kmeans_centers(hmx_ctx* ctx) {
   ctx->seed_cells.assign(gcells.begin(), gcells.end());   // diagnostics: hmx_get("seed_cells")
   CHK(gather_centres(ctx, gcells, d_gcells, d_rows));
   // 10 x one Lloyd iteration (:53-64); the centre update runs on the device, no host round trip per iteration
-  const bool tile_ok = D.tile_impl && (size_t)D.NQ * D.NS * 1024 + ((size_t)K * d + K) * 8 <= 160 * 1024;
+  // (the tile kernel stages the centroid image next to the K x d sum table; where both do not fit, k_lloyd sums into memory)
+  const bool tile_ok = (size_t)D.NQ * D.NS * 1024 + ((size_t)K * d + K) * 8 <= 160 * 1024;
   for (int it = 0; it < 10; it++) {
     if (it == 0) HIPCHK(hipMemsetAsync(D.lsum, 0, sizeof(long long) * ((size_t)K * d + K), ctx->L.stream));   // sums + counts: one buffer (k_lloyd_finish leaves it zeroed for the next iteration)
     if (tile_ok) { l_tile_static(ctx->L, D, 2); KCHK(); }

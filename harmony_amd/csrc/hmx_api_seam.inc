@@ -232,7 +232,7 @@ struct hmx_ctx {
   int64_t rounds_without_R = 0;
   int64_t carried_rounds = 0;
   bool chain_ok = false; int chain_wgs = 0; uint64_t chain_rounds = 0;   // persistent block chain (one launch per round)
-  int tun_impl = -1, tun_tpw = -1, tun_cpw = -1, tun_wps = -1;  // tunables set through hmx_set_int before setup
+  int tun_tpw = -1, tun_wps = -1;  // tunables set through hmx_set_int before setup
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool; size_t ev_used = 0;
   // GPU phase timers (profile mode): event pairs tagged with a phase name, named after the reference's Timer phases
   // (src/harmony.cpp:302-335,557-615) where a phase has a counterpart; resolved lazily into gpu_timers
@@ -479,8 +479,7 @@ int head_pass(hmx_ctx* ctx, bool normalise = false) {   // normalise: Z_corr <- 
   // files its R sums as that round's old contributions: no pass over R between the head and the first round either.
   const bool sharded_ = ctx->world > 1 || ctx->comm_force;
   // (the head of init_cluster_cpp too: the first round then finds its old contributions filed as well -- no pass over R at all)
-  const bool gather = ctx->carry_ok && ctx->injected.empty() && ctx->rng_mode == 0 && ctx->D.upd_impl == 0 &&
-                      ctx->D.tile_impl && (size_t)ctx->D.NQ * ctx->D.NS * 1024 <= 160 * 1024;
+  const bool gather = ctx->carry_ok && ctx->injected.empty() && ctx->rng_mode == 0;
   if (gather) {
     PhaseScope ph(ctx, "randomize");
     CHK(prepare_round(ctx, ctx->round_counter));     // (update_R finds this round sorted and the next one in flight)
@@ -489,9 +488,8 @@ int head_pass(hmx_ctx* ctx, bool normalise = false) {   // normalise: Z_corr <- 
   Dev D = ctx->D;
   ctx->head_is_stale = false;      // (dist_mat is recomputed here)
   ctx->objf_continued = true;      // (R is rewritten from the corrected embedding: the objective's warm starts are stale, its next evaluation takes a pass more up front)
-  const bool tiles = D.tile_impl && (size_t)D.NQ * D.NS * 1024 <= 160 * 1024;
   // the register-pipelined head (two accumulator sets, rows of a tile in registers) normalises the rows it has loaded anyway
-  const bool fused_norm = normalise && tiles && D.NT4 <= 4 && D.NCT <= 7 && D.upd_wps != 4;
+  const bool fused_norm = normalise && D.NT4 <= 4 && D.NCT <= 7 && D.upd_wps != 4;
   if (normalise && !fused_norm) { l_normalize(ctx->L, D.Zc, D.n, D.d, D.zs); KCHK(); }
   D.head_norm = fused_norm ? 1 : 0;
   for (int i = 0; i < 2; i++) if (ctx->sold_state[i] == 2) ctx->sold_state[i] = 1;     // R is rewritten: carried old contributions are void
@@ -510,12 +508,8 @@ int head_pass(hmx_ctx* ctx, bool normalise = false) {   // normalise: Z_corr <- 
   ctx->R_valid = false;
   // O, the contribution replicas, the objective slots (and a stale old-contribution table): ONE launch instead of three or four memsets
   l_zero4(ctx->L, D.O_fx, (size_t)D.B * D.K, D.Snew_fx, (size_t)D.nrep * D.B * D.K, D.objpart, 2 * (size_t)D.objslots * D.nwmax, zero_sold, n_sold); KCHK();
-  if (D.tile_impl && (size_t)D.NQ * D.NS * 1024 <= 160 * 1024) {
-    l_tile_static(ctx->L, D, 1); KCHK();      // MFMA tiles; O contributions land in the Snew replicas
-    l_fold(ctx->L, D, -1, 0); KCHK();         // O = sum of the replicas
-  } else {
-    l_head(ctx->L, D, 0); KCHK();
-  }
+  l_tile_static(ctx->L, D, 1); KCHK();      // MFMA tiles; O contributions land in the Snew replicas
+  l_fold(ctx->L, D, -1, 0); KCHK();         // O = sum of the replicas
   l_obj_reduce(ctx->L, D); KCHK();
   CHK(allreduce(ctx, D.O_fx, (int64_t)D.B * D.K, 0));
   CHK(allreduce(ctx, D.obj, 2, 1));

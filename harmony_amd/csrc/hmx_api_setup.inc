@@ -241,7 +241,6 @@ int hmx_setup_ex(hmx_ctx* ctx, const void* Z, int32_t z_dtype, int32_t z_locatio
   { const char* e = getenv("HMX_NREP"); int want = e ? atoi(e) : 8; if (want > 8) want = 8; D.nrep = 1; while (D.nrep * 2 <= want && (size_t)D.nrep * 2 * B * K <= (1u << 20)) D.nrep *= 2; }
   { static const int sup[] = {1, 2, 3, 4, 5, 6, 7, 8, 10, 12, 13, 14, 16};     // (13: K = 200, BASELINE configs[4])
     const int need = (K + 15) / 16; D.NCT = 16; for (int v : sup) if (v >= need) { D.NCT = v; break; } }
-  D.lloyd_lds = ((size_t)d * D.KP * 4 + ((size_t)K * d + K) * 8 <= 98304) ? 1 : 0;
   { const char* e = getenv("HMX_MOE_IMPL");
     D.moe_mfma = (K % 4 == 0 && d <= 64 && K <= 256 && !(e && std::string(e) == "v1")) ? 1 : 0;   // K > 128: split statistics kernel
     D.wNT4 = K / 16; D.wtail = (K - 16 * D.wNT4) / 4; D.wNS = 4 * D.wNT4 + D.wtail; D.wNQ = ((d + 15) / 16 + 3) / 4; }
@@ -251,11 +250,13 @@ int hmx_setup_ex(hmx_ctx* ctx, const void* Z, int32_t z_dtype, int32_t z_locatio
   D.pen_lds = ((size_t)D.NQ * 0 + (size_t)B * K * 4 + (size_t)Q * C * 4 <= 24576) ? 1 : 0;
   D.rvec = (K % 4 == 0) ? 1 : 0;
   D.NQ = (D.NCT + 3) / 4; D.NT4 = D.zs / 16; D.tail = (D.zs - 16 * D.NT4) / 4; D.NS = 4 * D.NT4 + D.tail;
+  // the static-tile launches (head, seeding race, Lloyd) stage this centroid image in LDS: across the envelope (d <= 128, K <= 256) it is at most
+  // 4 quads x 32 PC steps x 1 KB = 128 KB, so they need no fallback (Lloyd's K x d sum table beside it may not fit: k_lloyd, hmx_api_kmeans.inc)
+  if ((size_t)D.NQ * D.NS * 1024 > 128 * 1024) return fail(ctx, HMX_ERR_LIMIT, "centroid image exceeds 128 KB of LDS");
   // split-bf16 form of the tile kernels' distance GEMM (hmx_tile_bf.hip): offered where its register form covers the shapes the fp32
   // register form covers (rows of <= 64 PCs in four 16-byte groups); each launch takes it when its LDS image fits (l_update & co)
   D.NS2 = (D.zs + 31) / 32;
   { const char* e = getenv("HMX_DOT"); D.dot_bf = !(e && std::string(e) == "f32") && (D.NT4 > 4 || D.NS2 <= 2) && D.NS2 <= 4; }
-  { const char* e = getenv("HMX_UPDATE_IMPL"); D.upd_impl = ctx->tun_impl >= 0 ? ctx->tun_impl : ((e && std::string(e) == "v1") ? 1 : 0); }
   { const char* e = getenv("HMX_UPD_THREADS"); D.upd_threads = (e && atoi(e) == 256) ? 256 : 512; }
   { // uniform sigma (the reference's default): scalar-constant kernel variants; with K <= 64 they also fit the register
     // budget of 4 waves per SIMD (1024-thread workgroups) -- measured 16 % faster per launch than 2 waves at K = 64
@@ -264,7 +265,7 @@ int hmx_setup_ex(hmx_ctx* ctx, const void* Z, int32_t z_dtype, int32_t z_locatio
     D.usig = usig ? 1 : 0;
     const char* e = getenv("HMX_UPD_WPS");
     int w = ctx->tun_wps > 0 ? ctx->tun_wps : (e ? atoi(e) : 4);
-    if (w != 4 || !usig || D.NCT > 4 || D.upd_impl != 0) w = 2;
+    if (w != 4 || !usig || D.NCT > 4) w = 2;
     D.upd_wps = w;
     if (w == 4) D.upd_threads = 1024; }
   { const char* e = getenv("HMX_UPD_MAXBLOCKS"); D.upd_maxblocks = e ? atoi(e) : (D.upd_threads >= 512 ? 256 : 512); if (D.upd_maxblocks < 1) D.upd_maxblocks = 1; }
@@ -273,9 +274,8 @@ int hmx_setup_ex(hmx_ctx* ctx, const void* Z, int32_t z_dtype, int32_t z_locatio
   // per SIMD the K > 64 kernels get) re-stages the centroid image once instead of four times: head 213 -> 200 us at 1M
   { const char* e = getenv("HMX_STATIC_MAXBLOCKS"); D.static_maxblocks = e ? atoi(e) : (D.NCT >= 5 ? 512 : D.NCT >= 3 ? 768 : 1024); }
   { const char* e = getenv("HMX_OLDSUM_IMPL"); D.oldsum_stream = (e && std::string(e) == "gather") ? 0 : (e && std::string(e) == "stream1") ? 2 : 1; }   // 1: 16-byte stream, 2: dword stream
-  D.need_lorder = (D.upd_impl == 1 || D.oldsum_stream == 0 || (size_t)D.nb * K * 8 > 64 * 1024) ? 1 : 0;
+  D.need_lorder = (D.oldsum_stream == 0 || (size_t)D.nb * K * 8 > 64 * 1024) ? 1 : 0;
   { const char* e = getenv("HMX_UPD_TPW"); D.upd_tpw = ctx->tun_tpw > 0 ? ctx->tun_tpw : (e ? atoi(e) : 1); if (D.upd_tpw < 1) D.upd_tpw = 1; }
-  { const char* e = getenv("HMX_UPD_CPW"); D.upd_cpw = ctx->tun_cpw > 0 ? ctx->tun_cpw : (e ? atoi(e) : 128); if (D.upd_cpw < 4) D.upd_cpw = 4; }
   std::vector<Item> schunks; std::vector<int> qchunk((size_t)Q + 1, 0);
   for (int q = 0; q < Q; q++) {
     qchunk[q] = (int)schunks.size();
@@ -286,7 +286,7 @@ int hmx_setup_ex(hmx_ctx* ctx, const void* Z, int32_t z_dtype, int32_t z_locatio
   { // Old contributions carried from round to round (update_R): tiles keyed by (block, combination, NEXT block) cost up to 16
     // padding slots per key -- worth it while the expected padding (8 per key) stays below 4 % (12 % with the chain) of the cells.  HMX_SOLD_CARRY=0|1.
     const char* e = getenv("HMX_SOLD_CARRY");
-    const bool fits = D.nb <= 63 && Q < (1 << 19) && D.upd_impl == 0 &&
+    const bool fits = D.nb <= 63 && Q < (1 << 19) &&
                       (int64_t)N + (int64_t)D.nb * D.nb * Q * 16 <= 2147483000ll;
     // (round 4: with the R stores of carried rounds gone as well -- Dev::r_store -- the carry saves ~200 us per round at 1M cells where the
     //  persistent chain runs (K <= 112): worth up to ~12 % of padding there; measured at 1.25M cells / 20 batches, 5.1 %: 15.5 -> 12.7 ms per run.
@@ -302,7 +302,6 @@ int hmx_setup_ex(hmx_ctx* ctx, const void* Z, int32_t z_dtype, int32_t z_locatio
     return fail(ctx, HMX_ERR_LIMIT, "padded block order (N + n_blocks * combinations * 16) exceeds the int32 index range of one shard");
   D.npad = (int)((int64_t)N + (int64_t)nV * Q * 16);
   D.nitems = (int)items.size(); D.naitems = (int)aitems.size(); D.ntitems = (int)titems.size();
-  { const char* e = getenv("HMX_TILE_IMPL"); D.tile_impl = (e && std::string(e) == "v1") ? 0 : 1; }
   CHK(dalloc(ctx, &D.Zo, (size_t)N * D.zs)); CHK(dalloc(ctx, &D.Zc, (size_t)N * D.zs)); CHK(dalloc(ctx, &D.R, ((size_t)N + 1) * K));   // + one dummy row (target of masked stores)
   CHK(dalloc(ctx, &D.perm, (size_t)N)); CHK(dalloc(ctx, &D.invperm, (size_t)N)); CHK(dalloc(ctx, &D.combo, (size_t)N));
   CHK(dalloc(ctx, &D.qlev, (size_t)Q * C));
@@ -418,7 +417,7 @@ int hmx_setup_ex(hmx_ctx* ctx, const void* Z, int32_t z_dtype, int32_t z_locatio
   ctx->W.assign((size_t)(B + 1) * d, 0.f); ctx->W_rows = B + 1;  // allocate_buffers :127
   ctx->Y.assign((size_t)d * K, 0.f);
   { const char* e = getenv("HMX_FUSED_FOLD");
-    ctx->fused_ok = !(e && std::string(e) == "0") && D.upd_impl == 0 &&
+    ctx->fused_ok = !(e && std::string(e) == "0") &&
                     (size_t)D.NQ * D.NS * 1024 + (size_t)B * K * 12 + (size_t)Q * C * 4 + 64 <= 150 * 1024; }
   { // persistent block chain: one workgroup per CU must be resident at once (they synchronise inside the launch)
     const char* e = getenv("HMX_CHAIN");
@@ -469,7 +468,7 @@ int hmx_setup_ex(hmx_ctx* ctx, const void* Z, int32_t z_dtype, int32_t z_locatio
       const size_t lds_f = ((size_t)2 * B * kw + kw) * 8;      // folders: [ O slice | cluster masses | this rank's deltas (sharded) ]
       const bool want = !(e && std::string(e) == "0") && !(pe && std::string(pe) == "0") && ((pe && std::string(pe) == "1") || (e && std::string(e) == "1") || tiles_per_stream <= max_tpw_pair);
       D.chain_pair = (want && !ctx->chain_ok && D.NCT > 7 && nctp >= 4 && nctp <= 7 && K % 4 == 0 && K - KH <= 16 * nctp && K - KH >= 4 && D.usig && D.dot_bf && D.NS2 <= 2 && D.NT4 <= 4 &&
-                      D.nb <= 64 && cus >= 64 && F < ctx->chain_wgs / 4 && D.upd_impl == 0 && !ctx->oe_arith && !ctx->obj_arith &&
+                      D.nb <= 64 && cus >= 64 && F < ctx->chain_wgs / 4 && !ctx->oe_arith && !ctx->obj_arith &&
                       std::max(lds_w, lds_f) + 64 <= 150 * 1024) ? 1 : 0;
       if (ctx->world > 1 || ctx->comm_force) {      // (the flag picks the inter-rank protocol of update_R: every rank takes the same path -- the minimum, as for chain_ok above)
         long long* dflag; long long hf = D.chain_pair;

@@ -39,7 +39,7 @@ int update_R(hmx_ctx* ctx) {
       ctx->sold_state[cur] = 1;
       if (!(chain_path && p2p)) CHK(allreduce(ctx, D.Sold_fx, (int64_t)nSold, 0));      // (p2p chain: the folder exchanges new(j - 1) - old_local(j), the ranks' old sums meet there)
       // this round's tile kernels collect the next round's old contributions if this round's tiles are keyed by the next block
-      const bool write_next = ctx->carry_ok && ctx->sorted_nxt[rnd & ctx->oset_mask] && !ctx->last_round_hint && D.upd_impl == 0;
+      const bool write_next = ctx->carry_ok && ctx->sorted_nxt[rnd & ctx->oset_mask] && !ctx->last_round_hint;
       D.Sold_next = nullptr;
       if (write_next) {
         if (ctx->sold_state[oth] != 0) HIPCHK(hipMemsetAsync(ctx->sold_buf[oth], 0, sizeof(long long) * nSold, ctx->L.stream));

@@ -21,13 +21,15 @@ constexpr double FX_INV = 1.0 / 536870912.0;
 // A run of cells (internal order) that share one covariate-level combination.
 struct Item { int q; int start; int cnt; };
 
-// Everything the kernels need; plain pointers, filled by the host side.
+// Everything the kernels need; plain pointers, filled by the host side.  (Field order: the kernels' code depends on the kernel-argument
+// offsets of the fields they read.  dot_bf, upd_wps and usig are read by the launchers only and sit where retired fields were, so that
+// every other field kept its offset modulo 16 and every kernel its register figures -- see tools/kernel_resources.py.)
 struct Dev {
   int n;            // local cells
   int d, K, B, C, Q;
   int B0;           // number of levels of covariate 0 (rowsum(R) = sum of its O columns)
   int cov_end[4];   // cumulative level counts of the first four covariates (B beyond the last one): which covariates a range of levels belongs to
-  int upd_cpw;      // cells per wave in the update kernel
+  int dot_bf;       // 1: tile kernels built for the split-bf16 form are launched where their LDS image fits (HMX_DOT=f32 turns it off)
   int KP;           // K rounded up to a multiple of 64
   int zs;           // row stride of Zo/Zc in floats: d rounded up to a multiple of 4 (16-byte rows), pads are 0
   // MFMA tile path (16 cells x 16 clusters x 4 PCs per v_mfma_f32_16x16x4_f32)
@@ -39,11 +41,7 @@ struct Dev {
   // bf16 parts in B-operand order [NCT][NS2][part][lane = 16 g + c][8 bf16] (PC j: step j >> 5, lane group g = (j & 31) >> 3, slot j & 7)
   int NS2;
   unsigned short* Yimg3;
-  int dot_bf;       // 1: tile kernels built for the split-bf16 form are launched where their LDS image fits (HMX_DOT=f32 turns it off)
-  int upd_impl;     // 0: MFMA tile kernel, 1: cluster-lane VALU kernel (v1)
   int upd_tpw;      // tiles per wave target of the MFMA update kernel
-  int upd_wps;      // waves per SIMD the update/head kernels are built for: 2 | 4 (lean: uniform sigma, K <= 64)
-  int usig;         // all clusters share one sigma (scalar-constant kernel variants)
   int static_maxblocks; // cap of the static-tile launches (head / Lloyd / seeding); 0 = nwmax / waves per workgroup
   // seeding race (k_tile mode 3): hash key, first global cell of this shard, cells already chosen (re-probe passes)
   unsigned long long seed_key, seed_goff; const unsigned* seed_excl; int seed_nexcl;
@@ -91,7 +89,7 @@ struct Dev {
   int* bincnt;                 // [keys * Q] cells of a (key, combination) bin before padding
   int* blkv;                   // [n] composite sort key of a cell (nxt)
   long long* Sold_next;        // [nb][B][K] old contributions of the NEXT round's blocks, filled by this round's tile kernels (or nullptr)
-  int need_lorder;             // the first-generation kernels (k_update, k_oldsum's gather variant) read lorder / lcombo; the tile kernels read lpair only
+  int need_lorder;             // k_oldsum's gather variant reads lorder / lcombo; the tile kernels read lpair only
   int upd_contig;              // k_tile MODE 0: a wave owns a contiguous range of the block's tiles (run-length flush) instead of every nw-th
   int qmask;                   // mask of the combination in a tile's combination word: 0x7FFFF if shuffles may be keyed by blocks, else 0x7FFFFFFF
   int head_gather;             // k_tile MODE 1 runs over the padded order of the upcoming round (lpair) instead of the static tiles
@@ -148,7 +146,7 @@ struct Dev {
   Item* items; int nitems;        // <= ITEM_CELLS cells each
   Item* aitems; int naitems;      // <= APPLY_CELLS cells each
   Item* titems; int ntitems;      // <= 16 cells each: static MFMA tiles (head, Lloyd)
-  int tile_impl;                  // 1: head / Lloyd run on the MFMA tile kernel, 0: cluster-lane VALU kernels
+  int upd_wps;      // waves per SIMD the update/head kernels are built for: 2 | 4 (lean: uniform sigma, K <= 64)
   // MoE
   double* Sq;       // [Q][K][d]  sum_i R_ki z_ij over cells of combination q
   double* nq;       // [Q][K]     sum_i R_ki
@@ -170,7 +168,7 @@ struct Dev {
   long long* km_gcells; double* km_rows; unsigned* km_excl;   // [K] chosen global cells, [K][d] their rows, [K] exclusion list
   unsigned long long* seedmin;  // [K] packed (key bits << 32 | global cell)
   long long* lsum;  // [K][d] 2^30 fixed-point sums of unit-vector components (exact, order-independent)
-  int lloyd_lds;    // 1: the Lloyd sums are accumulated in an LDS table per workgroup first
+  int usig;         // all clusters share one sigma (scalar-constant kernel variants)
   unsigned long long* lcnt;  // [K]
   float* ynorm;     // [K]
 };
@@ -206,8 +204,8 @@ void l_copy(const Launch& L, const float* src, float* dst, size_t count);
 void l_zero4(const Launch& L, void* a, size_t na, void* b, size_t nb, void* c, size_t nc, void* d, size_t nd);      // up to four buffers of 8-byte words, one launch
 void l_normalize(const Launch& L, float* Z, int n, int d, int zs);
 void l_normalize_from(const Launch& L, const float* src, float* dst, int n, int d, int zs);
-// mode 0: head (write R, accumulate O_fx, objective partials); mode 1: objective only (read R)
-void l_head(const Launch& L, const Dev& D, int mode);
+// objective partials of the current state (reads R)
+void l_head(const Launch& L, const Dev& D);
 void l_tile_static(const Launch& L, const Dev& D, int mode);
 void l_sort_blocks(const Launch& L, const Dev& D, bool fused, uint64_t seed, uint64_t round, uint64_t Nglob, uint64_t goff,
                    uint64_t cells_per_block);
@@ -301,7 +299,6 @@ void l_moe_apply(const Launch& L, const Dev& D);
 void l_moe_stats_mfma(const Launch& L, const Dev& D);
 void l_moe_solve(const Launch& L, const Dev& D, const SolveArgs& A);
 void l_moe_apply_mfma(const Launch& L, const Dev& D);
-void l_seed_probe(const Launch& L, const Dev& D, uint64_t seed, uint64_t goff, const unsigned* excl, int nexcl);
 void l_seed_race_u(const Launch& L, const Dev& D, const float* u, int a0, int na, int only, uint64_t goff, const unsigned* excl,
                    int nexcl);
 void l_gather_rows(const Launch& L, const Dev& D, const long long* gcells, uint64_t goff, double* rows);

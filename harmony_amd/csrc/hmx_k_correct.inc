@@ -1147,74 +1147,10 @@ __global__ __launch_bounds__(256) void k_moe_apply_mfma(Dev D) {
 }
 
 // --------------------------------------------------------------------------------------
-// kmeans_centers (src/utils.cpp:10-64)
-//   k_seed_probe: for every anchor i (= cluster lane) sample a cell with P ~ |2(1 - y_i.x)| via the
-//                 exponential race  argmin_n  -log(u_{i,n}) / dist_{i,n}   (:27-34), all K anchors
-//                 in ONE pass; result = packed (key bits, global cell) min per cluster.
-//   k_lloyd     : one Lloyd iteration: nearest centre (Euclidean), sums and counts.
+// kmeans_centers (src/utils.cpp:10-64): the seeding race and Lloyd run on the tile kernel (k_tile MODE 3 / 2, hmx_k_tile.inc);
+//   k_seed_race_u: the race on uniforms from the host;  k_lloyd: one Lloyd iteration where the K x d sum table does not fit
+//   the tile kernel's LDS.
 // --------------------------------------------------------------------------------------
-template <int KPL, int DPL>
-__global__ __launch_bounds__(TPB) void k_seed_probe(Dev D, uint64_t seed, uint64_t goff, const unsigned* __restrict__ excl,
-                                                    int nexcl) {
-  extern __shared__ __attribute__((aligned(16))) float ldsY[];
-  stage_Y(ldsY, D.Yt, D.d, D.K, D.KP);
-  constexpr int CB = 4;
-  const int lane = threadIdx.x & 63;
-  const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nw = (gridDim.x * blockDim.x) >> 6;
-  const int d = D.d, K = D.K;
-  uint64_t sk[KPL]; unsigned long long best[KPL];
-#pragma unroll
-  for (int q = 0; q < KPL; q++) {
-    sk[q] = splitmix64(seed ^ ((uint64_t)(1 + lane + 64 * q) * 0xD1342543DE82EF95ull));
-    best[q] = ~0ull;
-  }
-  for (int it = wave; it < D.nitems; it += nw) {
-    const Item item = D.items[it];
-    for (int p = 0; p < item.cnt; p += CB) {
-      const int nc = min(CB, item.cnt - p);
-      float z[CB][DPL];
-#pragma unroll
-      for (int c = 0; c < CB; c++) {
-        if (c < nc) load_row<DPL>(D.Zc, (size_t)(item.start + p + c), D.zs, d, lane, z[c]);
-        else {
-#pragma unroll
-          for (int t = 0; t < DPL; t++) z[c][t] = 0.0f;
-        }
-      }
-      float acc[CB][KPL];
-      group_dots<KPL, DPL, CB>(ldsY, d, D.KP, lane, z, acc);
-#pragma unroll
-      for (int c = 0; c < CB; c++) {
-        if (c < nc) {
-          const int cell = item.start + p + c;
-          const uint64_t g = goff + (uint64_t)D.perm[cell];
-          bool skip = false;
-          for (int x = 0; x < nexcl; x++) skip |= ((uint64_t)excl[x] == g);
-          if (!skip) {
-#pragma unroll
-            for (int q = 0; q < KPL; q++) {
-              if (lane + 64 * q < K) {
-                const float dis = fabsf(2.0f * (1.0f - acc[c][q]));
-                const uint64_t h = splitmix64(sk[q] + g);
-                const float u = ((float)(h >> 40) + 0.5f) * (1.0f / 16777216.0f);
-                const float key = -logf(u) / dis;  // >= 0 (or +inf / nan when dis == 0)
-                unsigned kb = __float_as_uint(key);
-                if (!(key >= 0.0f)) kb = 0x7f800000u;
-          kb &= 0x7fffffffu;   // -0.0 (u == 1: -log(u) = -0) must order as zero, not as the largest unsigned pattern  // nan -> +inf: never the minimum
-                const unsigned long long pk = ((unsigned long long)kb << 32) | (unsigned long long)(uint32_t)g;
-                best[q] = pk < best[q] ? pk : best[q];
-              }
-            }
-          }
-        }
-      }
-    }
-  }
-#pragma unroll
-  for (int q = 0; q < KPL; q++)
-    if (lane + 64 * q < K && best[q] != ~0ull) atomicMin(&D.seedmin[lane + 64 * q], best[q]);
-}
-
 // R-compatible seeding race (hmx_set_int "rng" = 1): the uniforms come from the HOST's stream (MT19937 seeded like set.seed, or
 // the host's unif_rand), u[a][local original cell] for the anchors a0 .. a0+na-1; per anchor the race of src/utils.cpp:24-34
 // over this shard's cells: key = -log(u) / |2(1 - y_a.x)|, index_min (ties -> the smaller global cell index).
@@ -1262,10 +1198,9 @@ __global__ void k_gather_rows(Dev D, const long long* __restrict__ gcells, uint6
 
 template <int KPL, int DPL>
 __global__ __launch_bounds__(TPB) void k_lloyd(Dev D) {
-  // LDS: [ centroids d*KP floats | (D.lloyd_lds) K*d 64-bit fixed-point sums + K counts ]
+  // LDS: centroids d*KP floats.  The K x d sums go straight to memory: this kernel runs only where the tile kernel's centroid image (zs*KP*4
+  // bytes) and the sum table exceed 160 KB together (hmx_api_kmeans.inc), so the table does not fit beside d*KP*4 bytes of centroids either.
   extern __shared__ __attribute__((aligned(16))) float ldsY[];
-  long long* ltab = reinterpret_cast<long long*>(ldsY + (((size_t)D.d * D.KP + 1) & ~(size_t)1));
-  if (D.lloyd_lds) for (int i = threadIdx.x; i < D.K * D.d + D.K; i += blockDim.x) ltab[i] = 0;
   stage_Y(ldsY, D.Yt, D.d, D.K, D.KP);
   constexpr int CB = 4;
   const int lane = threadIdx.x & 63;
@@ -1307,30 +1242,15 @@ __global__ __launch_bounds__(TPB) void k_lloyd(Dev D) {
           best = wmin64(best);
           const int kb = (int)(best & 0xffffffffu);
 #pragma unroll
-          // unit-vector components as 2^30 fixed point: exact, order-independent 64-bit sums (LDS-private per
-          // workgroup when the table fits, then one global atomic per entry)
+          // unit-vector components as 2^30 fixed point: exact, order-independent 64-bit sums
           for (int t = 0; t < DPL; t++) {
             const int jj = 64 * t + lane;
-            if (jj < d) {
-              const unsigned long long v = (unsigned long long)__float2ll_rn(z[c][t] * 1073741824.0f);
-              if (D.lloyd_lds) atomicAdd((unsigned long long*)&ltab[kb * d + jj], v);
-              else atomicAdd((unsigned long long*)&D.lsum[(size_t)kb * d + jj], v);
-            }
+            if (jj < d) atomicAdd((unsigned long long*)&D.lsum[(size_t)kb * d + jj], (unsigned long long)__float2ll_rn(z[c][t] * 1073741824.0f));
           }
-          if (lane == 0) {
-            if (D.lloyd_lds) atomicAdd((unsigned long long*)&ltab[K * d + kb], 1ull);
-            else atomicAdd(&D.lcnt[kb], 1ull);
-          }
+          if (lane == 0) atomicAdd(&D.lcnt[kb], 1ull);
         }
       }
     }
-  }
-  if (D.lloyd_lds) {
-    __syncthreads();
-    for (int i = threadIdx.x; i < K * d; i += blockDim.x)
-      if (ltab[i]) atomicAdd((unsigned long long*)&D.lsum[i], (unsigned long long)ltab[i]);
-    for (int i = threadIdx.x; i < K; i += blockDim.x)
-      if (ltab[K * d + i]) atomicAdd(&D.lcnt[i], (unsigned long long)ltab[K * d + i]);
   }
 }
 

@@ -19,26 +19,25 @@ static inline bool bf_fits(const Dev& D, size_t rest, long long blocks) {
 }
 
 #if !HMX_TILE_BF
-#define HMX_DISPATCH_KD(KERNEL, EXTRA, GRID, LDS, ...)                                         \
+#define HMX_DISPATCH_KD(KERNEL, GRID, LDS, ...)                                                \
   do {                                                                                         \
     const int kpl_ = D.KP / 64, dpl_ = D.d > 64 ? 2 : 1;                                       \
     if (dpl_ == 1) {                                                                           \
       switch (kpl_) {                                                                          \
-        case 1: hipLaunchKernelGGL((KERNEL<1, 1 EXTRA>), GRID, dim3(TPB), LDS, L.stream, __VA_ARGS__); break; \
-        case 2: hipLaunchKernelGGL((KERNEL<2, 1 EXTRA>), GRID, dim3(TPB), LDS, L.stream, __VA_ARGS__); break; \
-        case 3: hipLaunchKernelGGL((KERNEL<3, 1 EXTRA>), GRID, dim3(TPB), LDS, L.stream, __VA_ARGS__); break; \
-        default: hipLaunchKernelGGL((KERNEL<4, 1 EXTRA>), GRID, dim3(TPB), LDS, L.stream, __VA_ARGS__); break; \
+        case 1: hipLaunchKernelGGL((KERNEL<1, 1>), GRID, dim3(TPB), LDS, L.stream, __VA_ARGS__); break; \
+        case 2: hipLaunchKernelGGL((KERNEL<2, 1>), GRID, dim3(TPB), LDS, L.stream, __VA_ARGS__); break; \
+        case 3: hipLaunchKernelGGL((KERNEL<3, 1>), GRID, dim3(TPB), LDS, L.stream, __VA_ARGS__); break; \
+        default: hipLaunchKernelGGL((KERNEL<4, 1>), GRID, dim3(TPB), LDS, L.stream, __VA_ARGS__); break; \
       }                                                                                        \
     } else {                                                                                   \
       switch (kpl_) {                                                                          \
-        case 1: hipLaunchKernelGGL((KERNEL<1, 2 EXTRA>), GRID, dim3(TPB), LDS, L.stream, __VA_ARGS__); break; \
-        case 2: hipLaunchKernelGGL((KERNEL<2, 2 EXTRA>), GRID, dim3(TPB), LDS, L.stream, __VA_ARGS__); break; \
-        case 3: hipLaunchKernelGGL((KERNEL<3, 2 EXTRA>), GRID, dim3(TPB), LDS, L.stream, __VA_ARGS__); break; \
-        default: hipLaunchKernelGGL((KERNEL<4, 2 EXTRA>), GRID, dim3(TPB), LDS, L.stream, __VA_ARGS__); break; \
+        case 1: hipLaunchKernelGGL((KERNEL<1, 2>), GRID, dim3(TPB), LDS, L.stream, __VA_ARGS__); break; \
+        case 2: hipLaunchKernelGGL((KERNEL<2, 2>), GRID, dim3(TPB), LDS, L.stream, __VA_ARGS__); break; \
+        case 3: hipLaunchKernelGGL((KERNEL<3, 2>), GRID, dim3(TPB), LDS, L.stream, __VA_ARGS__); break; \
+        default: hipLaunchKernelGGL((KERNEL<4, 2>), GRID, dim3(TPB), LDS, L.stream, __VA_ARGS__); break; \
       }                                                                                        \
     }                                                                                          \
   } while (0)
-#define HMX_COMMA ,
 
 static int stream_grid(const Launch& L, long long work_waves) {
   long long blocks = (work_waves + 3) / 4;
@@ -98,8 +97,9 @@ void HMX_LNAME(l_tile_static)(const Launch& L, const Dev& D, int mode) {
   const dim3 grid((unsigned)blocks);
 #if HMX_TILE_BF
   // Lloyd, one workgroup per CU (image + K x d sum table: 84 KB): THREE waves per SIMD -- the kernel needs 150 registers, and the MFMA chain, the
-  // arg-min and the LDS sums of a tile run one after the other on one accumulator set: a third wave fills the gaps (HMX_LLOYD_WPS=2: 512 threads)
-  if (mode == 2 && thr == 512 && D.NCT >= 5 && D.NCT <= 7 && !(getenv("HMX_LLOYD_WPS") && atoi(getenv("HMX_LLOYD_WPS")) == 2)) {
+  // arg-min and the LDS sums of a tile run one after the other on one accumulator set: a third wave fills the gaps (round 6: 0.13 ms of 1.69 per
+  // k-means initialisation at 1M cells against two waves per SIMD)
+  if (mode == 2 && thr == 512 && D.NCT >= 5 && D.NCT <= 7) {
     switch (D.NCT) {
       case 5: hipLaunchKernelGGL((k_tile<5, 2, 3>), grid, dim3(768), lds, L.stream, D, 0); break;
       case 6: hipLaunchKernelGGL((k_tile<6, 2, 3>), grid, dim3(768), lds, L.stream, D, 0); break;
@@ -130,11 +130,8 @@ void HMX_LNAME(l_tile_static)(const Launch& L, const Dev& D, int mode) {
 #undef HMX_TSL
 }
 #if !HMX_TILE_BF
-void l_head(const Launch& L, const Dev& D, int mode) {
-  const dim3 grid(stream_grid(L, D.nitems));
-  const size_t lds = lds_bytes_y(D);
-  if (mode == 0) HMX_DISPATCH_KD(k_head, HMX_COMMA 0, grid, lds, D);
-  else HMX_DISPATCH_KD(k_head, HMX_COMMA 1, grid, lds, D);
+void l_head(const Launch& L, const Dev& D) {
+  HMX_DISPATCH_KD(k_head, dim3(stream_grid(L, D.nitems)), lds_bytes_y(D), D);
 }
 // fused = true: D.blk is produced by the histogram kernel from (seed, round); false: the host uploaded D.blk (injected shuffle)
 static SortPtrs sort_ptrs_of(const Dev& D) { return SortPtrs{D.blk, D.blkv, D.counts, D.offs, D.binoff, D.bincnt, D.boff, D.lorder, D.lcombo, D.lpair}; }
@@ -381,17 +378,6 @@ void l_obj_reduce(const Launch& L, const Dev& D) {
     else hipLaunchKernelGGL(KERNEL, GRID, BLOCK, LDS, L.stream, __VA_ARGS__);                                              \
   } while (0)
 void HMX_LNAME(l_update)(const Launch& L, const Dev& D, int j) {
-#if !HMX_TILE_BF
-  if (D.upd_impl == 1) {
-    // a block holds ~n/nb cells; D.upd_cpw cells per wave (tunable: HMX_UPD_CPW)
-    const long long waves = ((long long)D.n / (D.nb > 0 ? D.nb : 1) + D.upd_cpw - 1) / D.upd_cpw + 1;
-    const dim3 grid(stream_grid(L, waves));
-    if (L.ev0) (void)hipEventRecord(L.ev0, L.stream);       // (profile mode: the first-generation kernel is launched plainly, the pair is recorded around it)
-    HMX_DISPATCH_KD(k_update, , grid, lds_bytes_y(D), D, j);
-    if (L.ev1) (void)hipEventRecord(L.ev1, L.stream);
-    return;
-  }
-#endif
   const long long tiles = ((long long)D.n / (D.nb > 0 ? D.nb : 1) + 15) / 16 + (long long)D.Q + 1;
   const int wpb = D.upd_threads / 64;
   long long blocks = ((tiles + D.upd_tpw - 1) / D.upd_tpw + wpb - 1) / wpb;
@@ -642,7 +628,7 @@ void l_objective_tables(const Launch& L, const Dev& D) {
 // false: shape outside this kernel's envelope (the caller falls back to the cluster-lane version)
 bool l_obj_terms_mfma(const Launch& L, const Dev& D, const float* M, float* T, long long stride, int all3) {
   const size_t lds = (size_t)D.NQ * D.NS * 64 * sizeof(f32x4);
-  if (!D.tile_impl || D.K % 4 != 0 || lds > 64 * 1024 || !D.Yimg || D.obj_stale || D.NT4 > 4) return false;      // (rows of <= 64 + 3 PCs in registers)
+  if (D.K % 4 != 0 || lds > 64 * 1024 || !D.Yimg || D.obj_stale || D.NT4 > 4) return false;      // (rows of <= 64 + 3 PCs in registers)
   int blocks = ((D.n + 15) / 16 + 3) / 4; if (blocks > 1024) blocks = 1024; if (blocks < 1) blocks = 1;
   // all3 == 2 (round 6): T = dist_mat itself, for the rounds of one cluster_cpp call (the three-array form is a template parameter nobody instantiates any more)
 #define HMX_OT(N) case N: if (all3 == 2) hipLaunchKernelGGL((k_obj_terms_mfma<N, false, true>), dim3(blocks), dim3(256), lds, L.stream, D, M, T, stride); \
@@ -676,7 +662,7 @@ void l_moe_apply(const Launch& L, const Dev& D) {
   int g = D.naitems < 4 * L.grid ? D.naitems : 4 * L.grid;
   if (g < 1) g = 1;
   const dim3 grid(g);
-  HMX_DISPATCH_KD(k_moe_apply, , grid, lds, D);
+  HMX_DISPATCH_KD(k_moe_apply, grid, lds, D);
 }
 void l_moe_solve(const Launch& L, const Dev& D, const SolveArgs& A0) {
   SolveArgs A = A0;
@@ -700,10 +686,9 @@ void l_moe_stats_mfma(const Launch& L, const Dev& D) {
   if (D.st_dma) {   // 16-byte operand loads + deterministic slot reduction (K <= 128)
     const dim3 grid((unsigned)D.st_nwg, (unsigned)D.st_halves), block(64 * ((D.d + 16) / 16));   // PC tiles incl. the ones column at index d; y: the halves of the clusters (K > 128)
     const int nct_q = D.st_halves == 2 ? (D.st_KH + 15) / 16 : D.NCT;
-    // (round 6) fp64 shadow sums in LDS + operands one tile ahead where two workgroups still fit a CU next to them (HMX_MOE_STATS=regs: the round-3 form)
+    // (round 6) fp64 shadow sums in LDS + operands one tile ahead where two workgroups still fit a CU next to them (else the round-3 form)
     const size_t shl = (size_t)(block.x / 64) * nct_q * 4 * 64 * sizeof(double);
-    static const bool regs_only = [] { const char* e = getenv("HMX_MOE_STATS"); return e && std::string(e) == "regs"; }();
-    const bool use_shl = !regs_only && 2 * shl <= 150 * 1024;
+    const bool use_shl = 2 * shl <= 150 * 1024;
 #define HMX_MSQ(N) case N: if (use_shl) hipLaunchKernelGGL((k_moe_stats_q<N, true>), grid, block, shl, L.stream, D, D.st_cpw); \
                            else hipLaunchKernelGGL((k_moe_stats_q<N>), grid, block, 0, L.stream, D, D.st_cpw); break;
     switch (nct_q) { HMX_MSQ(1) HMX_MSQ(2) HMX_MSQ(3) HMX_MSQ(4) HMX_MSQ(5) HMX_MSQ(6) HMX_MSQ(7) HMX_MSQ(8) default: break; }
@@ -738,10 +723,6 @@ void l_moe_apply_mfma(const Launch& L, const Dev& D) {
     default: hipLaunchKernelGGL(k_moe_apply_mfma<4>, grid, dim3(256), lds, L.stream, D); break;
   }
 }
-void l_seed_probe(const Launch& L, const Dev& D, uint64_t seed, uint64_t goff, const unsigned* excl, int nexcl) {
-  const dim3 grid(stream_grid(L, D.nitems));
-  HMX_DISPATCH_KD(k_seed_probe, , grid, lds_bytes_y(D), D, seed, goff, excl, nexcl);
-}
 void l_seed_race_u(const Launch& L, const Dev& D, const float* u, int a0, int na, int only, uint64_t goff, const unsigned* excl,
                    int nexcl) {
   int blocks = (D.n + 255) / 256; if (blocks > 1024) blocks = 1024; if (blocks < 1) blocks = 1;
@@ -756,12 +737,7 @@ void l_lloyd_finish(const Launch& L, const Dev& D) {
   hipLaunchKernelGGL(k_lloyd_finish, dim3(D.K), dim3(64), 0, L.stream, D);
 }
 void l_lloyd(const Launch& L, const Dev& D) {
-  int blocks = stream_grid(L, D.nitems);
-  if (D.lloyd_lds && blocks > 512) blocks = 512;  // every workgroup flushes a K x d table: keep them few and fat
-  const dim3 grid(blocks);
-  const size_t lds = (((size_t)D.d * D.KP + 1) & ~(size_t)1) * sizeof(float) +
-                     (D.lloyd_lds ? ((size_t)D.K * D.d + D.K) * sizeof(long long) : 0);
-  HMX_DISPATCH_KD(k_lloyd, , grid, lds, D);
+  HMX_DISPATCH_KD(k_lloyd, dim3(stream_grid(L, D.nitems)), lds_bytes_y(D), D);
 }
 
 #endif  // !HMX_TILE_BF

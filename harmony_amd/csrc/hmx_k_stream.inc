@@ -1,5 +1,5 @@
-// hmx_k_stream.inc -- part of hmx_kernels.hip (included inside namespace hmx): ingest / egress, the first-generation head, the rounds' shuffle (counting sort and
-// the sort-free form), the old-contribution passes, fold / penalty kernels, the first-generation block update.  Not built into the split-bf16 unit.
+// hmx_k_stream.inc -- part of hmx_kernels.hip (included inside namespace hmx): ingest / egress, the objective of the current state, the rounds' shuffle
+// (counting sort and the sort-free form), the old-contribution passes, fold / penalty kernels.  Not built into the split-bf16 unit.
 #if !HMX_TILE_BF   // (the split-bf16 translation unit builds k_tile and its launchers only)
 // --------------------------------------------------------------------------------------
 // src: [n][d] doubles or floats in local original order (host slab staged in HBM, or the caller's device buffer)
@@ -51,12 +51,11 @@ __global__ __launch_bounds__(TPB) void k_normalize(float* __restrict__ Z, int n,
 }
 
 // --------------------------------------------------------------------------------------
-// E-step head: dist = 2(1 - Y^T Z), R = softmax_k(-dist/sigma), O, objective partials
-// (src/harmony.cpp:141-150 and :221-227).  One wave per static work item (a run of cells
-// with one combination).  MODE 0: write R and accumulate O_fx.  MODE 1: objective only,
-// R is read (harmony::compute_objective on the current state).
+// Objective partials of the current state (harmony::compute_objective, src/harmony.cpp:158-170):
+// dist = 2(1 - Y^T Z) (:141) against the R rows as they stand.  One wave per static work item (a run
+// of cells with one combination).
 // --------------------------------------------------------------------------------------
-template <int KPL, int DPL, int MODE>
+template <int KPL, int DPL>
 __global__ __launch_bounds__(TPB) void k_head(Dev D) {
   extern __shared__ __attribute__((aligned(16))) float ldsY[];
   stage_Y(ldsY, D.Yt, D.d, D.K, D.KP);
@@ -70,9 +69,6 @@ __global__ __launch_bounds__(TPB) void k_head(Dev D) {
   double od = 0.0, oe = 0.0;
   for (int it = wave; it < D.nitems; it += nw) {
     const Item item = D.items[it];
-    unsigned long long oacc[KPL];
-#pragma unroll
-    for (int q = 0; q < KPL; q++) oacc[q] = 0ull;
     for (int p = 0; p < item.cnt; p += CB) {
       const int nc = min(CB, item.cnt - p);
       float z[CB][DPL];
@@ -91,29 +87,11 @@ __global__ __launch_bounds__(TPB) void k_head(Dev D) {
         if (c < nc) {
           const size_t cell = (size_t)(item.start + p + c);
           float r[KPL], dist[KPL];
-          if (MODE == 0) {
-            float s = 0.0f;
 #pragma unroll
-            for (int q = 0; q < KPL; q++) {
-              const int k = lane + 64 * q;
-              dist[q] = 2.0f * (1.0f - acc[c][q]);
-              r[q] = (k < K) ? expf(-dist[q] / sig[q]) : 0.0f;
-              s += r[q];
-            }
-            s = wsum(s);
-#pragma unroll
-            for (int q = 0; q < KPL; q++) {
-              const int k = lane + 64 * q;
-              r[q] = r[q] / s;
-              if (k < K) { D.R[cell * K + k] = r[q]; oacc[q] += fx_of(r[q]); }
-            }
-          } else {
-#pragma unroll
-            for (int q = 0; q < KPL; q++) {
-              const int k = lane + 64 * q;
-              dist[q] = 2.0f * (1.0f - acc[c][q]);
-              r[q] = ld_or(D.R, cell * K + min(k, K - 1), k < K, 0.0f);
-            }
+          for (int q = 0; q < KPL; q++) {
+            const int k = lane + 64 * q;
+            dist[q] = 2.0f * (1.0f - acc[c][q]);
+            r[q] = ld_or(D.R, cell * K + min(k, K - 1), k < K, 0.0f);
           }
 #pragma unroll
           for (int q = 0; q < KPL; q++) {
@@ -125,7 +103,6 @@ __global__ __launch_bounds__(TPB) void k_head(Dev D) {
         }
       }
     }
-    if (MODE == 0) flush_fx<KPL>(D.O_fx, D.qlev, item.q, D.C, K, lane, oacc);
   }
   od = wsumd(od); oe = wsumd(oe);
   if (lane == 0) { D.objpart[2 * wave] += od; D.objpart[2 * wave + 1] += oe; }  // private slot (slot row 0): no atomics
@@ -469,18 +446,14 @@ __global__ __launch_bounds__(1024) void k_shuf_place(Dev D, ShufBatch S) {
 }
 
 // --------------------------------------------------------------------------------------
-// update_R (src/harmony.cpp:269-342) split into:
-//   k_oldsum   one pass: old contribution of EVERY block of this round (:312-313 for all blocks)
-//   k_prepare  tiny: O <- O + new(prev block) - old(this block); penalty table (:322)
-//   k_update   the block's cells: R <- normalise(exp(-dist/sigma)); R *= penalty; normalise;
-//              accumulate the new contribution (:318-330) and the objective partials (:160-161)
+// update_R (src/harmony.cpp:269-342): the streaming passes around the block update (k_tile MODE 0, hmx_k_tile.inc)
+//   k_oldsum*  one pass: old contribution of EVERY block of this round (:312-313 for all blocks)
+//   k_fold / k_penalty, k_foldpen   O <- O + new(prev block) - old(this block); penalty table (:322)
+//   k_obj_reduce / k_obj_final      the objective partials of the wave slots -> obj[0..1]
 // --------------------------------------------------------------------------------------
-#ifndef HMX_OLDSUM_CB
-#define HMX_OLDSUM_CB 4
-#endif
 template <int KPL>
 __global__ __launch_bounds__(TPB) void k_oldsum(Dev D) {
-  constexpr int CB = HMX_OLDSUM_CB;
+  constexpr int CB = 4;
   const int lane = threadIdx.x & 63;
   const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nw = (gridDim.x * blockDim.x) >> 6;
   const int K = D.K;
@@ -601,10 +574,8 @@ __global__ __launch_bounds__(1024) void k_oldsum_stream4(Dev D) {
       const unsigned long long v = otab[i];
       if (v) {
         const int blk = i / K, kp = i - blk * K, k = (kp % K4) * 4 + kp / K4;
-#ifndef HMX_OS_NOFLUSH
         for (int cc = 0; cc < D.C; cc++)
           atomicAdd((unsigned long long*)&D.Sold_fx[((size_t)blk * D.B + D.qlev[q * D.C + cc]) * K + k], v);
-#endif
         otab[i] = 0ull;
       }
     }
@@ -727,87 +698,6 @@ __global__ void k_penalty(Dev D) {
   const float o = (float)((double)D.O_fx[i] * FX_INV);
   const float e = (float)(((double)rs * FX_INV) * (double)D.Pr_b[b]);
   D.pen[i] = pen_pow((2.0f * e) + 1.0f, o + e + 1.0f, D.theta[b]);
-}
-
-template <int KPL, int DPL>
-__global__ __launch_bounds__(TPB) void k_update(Dev D, int j) {
-  extern __shared__ __attribute__((aligned(16))) float ldsY[];
-  stage_Y(ldsY, D.Yt, D.d, D.K, D.KP);
-  constexpr int CB = 4;
-  const int lane = threadIdx.x & 63;
-  const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nw = (gridDim.x * blockDim.x) >> 6;
-  const int d = D.d, K = D.K;
-  const int p0 = D.boff[j], p1 = D.boff[j + 1];
-  const int per = (p1 - p0 + nw - 1) / nw;
-  const int s = p0 + wave * per, e = min(p1, s + per);
-  if (s >= e) return;
-  float sig[KPL], penv[KPL];
-  unsigned long long oacc[KPL];
-#pragma unroll
-  for (int q = 0; q < KPL; q++) { sig[q] = ld_or(D.sigma, (size_t)min(lane + 64 * q, K - 1), lane + 64 * q < K, 1.0f); penv[q] = 0.0f; oacc[q] = 0ull; }
-  double od = 0.0, oe = 0.0;
-  int curq = -1;
-  for (int p = s; p < e; p += CB) {
-    const int nc = min(CB, e - p);
-    int cell[CB]; float z[CB][DPL];
-#pragma unroll
-    for (int c = 0; c < CB; c++) {
-      cell[c] = ld_or(D.lorder, (size_t)min(p + c, e - 1), c < nc, -1);  // -1: padding slot
-      if (cell[c] >= 0) load_row<DPL>(D.Zc, (size_t)cell[c], D.zs, d, lane, z[c]);
-      else {
-#pragma unroll
-        for (int t = 0; t < DPL; t++) z[c][t] = 0.0f;
-      }
-    }
-    float acc[CB][KPL];
-    group_dots<KPL, DPL, CB>(ldsY, d, D.KP, lane, z, acc);
-#pragma unroll
-    for (int c = 0; c < CB; c++) {
-      if (cell[c] >= 0) {
-        const int q0 = D.combo[cell[c]];
-        if (q0 != curq) {
-          if (curq >= 0) flush_fx<KPL>(D.Snew_fx, D.qlev, curq, D.C, K, lane, oacc);
-          curq = q0;
-#pragma unroll
-          for (int q = 0; q < KPL; q++) penv[q] = 0.0f;
-          for (int cc = 0; cc < D.C; cc++) {  // penalty of a cell = SUM over its covariates (:322 is a matrix product)
-            const int b = D.qlev[q0 * D.C + cc];
-#pragma unroll
-            for (int q = 0; q < KPL; q++) if (lane + 64 * q < K) penv[q] += D.pen[(size_t)b * K + lane + 64 * q];
-          }
-        }
-        float r[KPL], dist[KPL];
-        float s1 = 0.0f;
-#pragma unroll
-        for (int q = 0; q < KPL; q++) {
-          dist[q] = 2.0f * (1.0f - acc[c][q]);
-          r[q] = (lane + 64 * q < K) ? expf(-dist[q] / sig[q]) : 0.0f;
-          s1 += fabsf(r[q]);
-        }
-        s1 = wsum(s1);
-        if (s1 == 0.0f) s1 = 1.0f;
-        float s2 = 0.0f;
-#pragma unroll
-        for (int q = 0; q < KPL; q++) { r[q] = (r[q] / s1) * penv[q]; s2 += fabsf(r[q]); }
-        s2 = wsum(s2);
-        if (s2 == 0.0f) s2 = 1.0f;
-#pragma unroll
-        for (int q = 0; q < KPL; q++) {
-          const int k = lane + 64 * q;
-          r[q] = r[q] / s2;
-          if (k < K) {
-            D.R[(size_t)cell[c] * K + k] = r[q];
-            oacc[q] += fx_of(r[q]);
-            od += (double)(r[q] * dist[q]);
-            oe += (double)((r[q] * trunc_logf_dev(r[q])) * sig[q]);
-          }
-        }
-      }
-    }
-  }
-  if (curq >= 0) flush_fx<KPL>(D.Snew_fx, D.qlev, curq, D.C, K, lane, oacc);
-  od = wsumd(od); oe = wsumd(oe);
-  if (lane == 0) { D.objpart[2 * wave] += od; D.objpart[2 * wave + 1] += oe; }  // private slot (slot row 0): no atomics
 }
 
 #endif  // !HMX_TILE_BF

@@ -31,16 +31,11 @@ __device__ __forceinline__ float dpp_f(float v, const int ctrl_id) {
 }
 // sum over the 16 lanes of a DPP row (lanes sharing l>>4); every lane gets the total
 __device__ __forceinline__ float rowsum16(float v) {
-#if HMX_USE_DPP
   v += dpp_f(v, 0);
   v += dpp_f(v, 1);
   v += dpp_f(v, 2);
   v += dpp_f(v, 3);
   return v;
-#else
-  v += __shfl_xor(v, 1, 64); v += __shfl_xor(v, 2, 64); v += __shfl_xor(v, 4, 64); v += __shfl_xor(v, 8, 64);
-  return v;
-#endif
 }
 
 // arma::normalise(Z, 2, 0) with 16-byte accesses: 16 lanes per row (lane c: float4 c [and c + 16]), four rows per wave instruction, four
@@ -83,7 +78,6 @@ __global__ __launch_bounds__(TPB) void k_normalize4(const float* Zsrc, float* Z,
 // N independent row sums, the DPP steps interleaved (ILP N: see epi_rows)
 template <int N>
 __device__ __forceinline__ void rowsum16xN(float (&v)[N]) {
-#if HMX_USE_DPP
 #pragma unroll
   for (int st = 0; st < 4; st++) {
     float t[N];
@@ -92,10 +86,6 @@ __device__ __forceinline__ void rowsum16xN(float (&v)[N]) {
 #pragma unroll
     for (int i = 0; i < N; i++) v[i] += t[i];
   }
-#else
-#pragma unroll
-  for (int i = 0; i < N; i++) v[i] = rowsum16(v[i]);
-#endif
 }
 
 template <int NCT>
@@ -507,7 +497,7 @@ __global__ __launch_bounds__(256 * WPS) void k_tile(Dev D, int j) {
     const int wpg = (int)blockDim.x >> 6, wib = (int)threadIdx.x >> 6, half = wpg >> 1, nwg = (int)gridDim.x - 1;
     // (second waves numbered workgroup-minor: the few SIMDs that must take a fourth tile are spread one per workgroup instead of
     //  filling whole CUs -- a CU's store / atomic queues are shared by its SIMDs)
-    if (HMX_CHAIN_BALANCE && half >= 1) wave_ = (wib < half) ? (int)blockIdx.x * half + wib : nwg * half + (wib - half) * nwg + (int)blockIdx.x;
+    if (half >= 1) wave_ = (wib < half) ? (int)blockIdx.x * half + wib : nwg * half + (wib - half) * nwg + (int)blockIdx.x;
   }
   const int wave = __builtin_amdgcn_readfirstlane(wave_);
   auto stamp = [&](int slot) {  // diagnostics build only (-DHMX_TRACE, tools/trace_update.py): per-wave phase stamps
@@ -1084,7 +1074,7 @@ __global__ __launch_bounds__(256 * WPS) void k_tile(Dev D, int j) {
       for (int reg = 0; reg < 4; reg++)
         if (c == 0 && cellr[reg] >= 0) atomicAdd((unsigned long long*)&ltab[K * dd + kb[reg]], 1ull);
     } else if constexpr (MODE == 3) {
-      // same arithmetic per (cell, anchor) as k_seed_probe: u from splitmix64(anchor key + global cell), key = -log(u) / dist
+      // exponential race of every anchor (src/utils.cpp:24-34): u from splitmix64(anchor key + global cell), key = -log(u) / |dist|
       int gc[4]; bool ok[4];
 #pragma unroll
       for (int reg = 0; reg < 4; reg++) {
@@ -1537,7 +1527,9 @@ __global__ __launch_bounds__(256 * WPS) void k_tile(Dev D, int j) {
       if constexpr (NOSTORE) { if (rows2_ok) rowsN = rowsN2; else ld_rows(next_rows(cellN, cellC), rowsN); }
       else ld_rows(next_rows(cellN, cellC), rowsN);
       dots_regs(rowsA, cellC.x >= 0, accC);
-      have2 = HMX_CHAIN_PRE2 && HMX_PAIR_PRE2(PAIR) && USIG && ts + tstep < te;    // (the general-sigma variant has no registers to spare: 95 spills)
+      // (the general-sigma variant has no registers to spare: 95 spills.  The wave-pair chain hoists ONE tile: with the second accumulator set live across
+      //  the flag as well it needs 87 spilled registers instead of 13 and a block step at K = 200 takes 44.8 instead of 42.6 us, profiles/r6_pair_chain_tuning.txt)
+      have2 = !PAIR && USIG && ts + tstep < te;
     };
     auto first_tile_b = [&]() __attribute__((always_inline)) {
       if (have2) {
@@ -1552,7 +1544,7 @@ __global__ __launch_bounds__(256 * WPS) void k_tile(Dev D, int j) {
     // both hoisted tiles against one read of the centroid image, when the second tile's rows are in registers already (MODE 5: rowsN2)
     auto first_tiles = [&]() __attribute__((always_inline)) {
       if constexpr (NOSTORE && BF) {
-        if (rows2_ok && HMX_CHAIN_PRE2 && USIG && ts + tstep < te) {
+        if (rows2_ok && USIG && ts + tstep < te) {
           cellC = cellN; cellS = cellNN;
           const RowRegs rowsA = rowsN, rowsB = rowsN2;
           cellN = tile_cell(ts + 2 * tstep); cellNN = tile_cell(ts + 3 * tstep);

@@ -14,25 +14,8 @@
 #include <float.h>
 #include <hip/hip_ext.h>
 
-#ifndef HMX_USE_DPP
-#define HMX_USE_DPP 1
-#endif
-#ifndef HMX_CHAIN_PRE2
-#define HMX_CHAIN_PRE2 1      // the chain runs the MFMAs of a wave's second tile of a block ahead of the flag too
-#endif
-#ifndef HMX_PAIR_PRE2
-// the wave-pair chain (MODE 6) hoists ONE tile's MFMAs ahead of the flag: with the second accumulator set live across the flag as well the kernel needs 87
-// spilled registers instead of 13 and a block step at K = 200 takes 44.8 instead of 42.6 us (profiles/r6_pair_chain_tuning.txt)
-#define HMX_PAIR_PRE2(PAIR) (!(PAIR))
-#endif
-#ifndef HMX_CHAIN_BALANCE
-#define HMX_CHAIN_BALANCE 1
-#endif
 #ifndef HMX_TILE_BF
 #define HMX_TILE_BF 0         // 1 (hmx_tile_bf.hip): this translation unit builds ONLY k_tile, with the split-bf16 distance GEMM, and its three launchers
-#endif
-#ifndef HMX_TILE_LB
-#define HMX_TILE_LB(NCT) 1   // waves/SIMD the tile kernel is register-budgeted for; 3 measured slower than unconstrained
 #endif
 
 namespace hmx {

@@ -20,10 +20,10 @@ extern "C" {
  * writable fields: "ridge_arith" / "oe_arith" / "obj_arith" / "solve_arith" (the accumulator groups of "ref_arith" one by one, before setup),
  * "seq_passes" / "seq_warm_passes" / "seq_tol_ppb" / "seq_strict" / "seq_stats" / "seq_max_passes" / "seq_fused" (see "reference arithmetic" below).
  * Tuning / fallback selectors (tests and measurements; the defaults are the measured best):
- *   fields "grid", "upd_wps" (before setup), "upd_tpw", "upd_cpw", "upd_impl", "comm_force";
+ *   fields "grid", "upd_wps" (before setup), "upd_tpw", "comm_force";
  *   environment, read by hmx_setup: HMX_GRID, HMX_NREP, HMX_UPD_WPS (2|4), HMX_USIG=0 (general-sigma kernels),
- *   HMX_UPD_THREADS, HMX_UPD_MAXBLOCKS, HMX_STATIC_MAXBLOCKS, HMX_UPD_TPW, HMX_UPD_CPW, HMX_FUSED_FOLD=0, HMX_FOLD_IMPL=split,
- *   HMX_OLDSUM_IMPL=gather|stream1, HMX_UPDATE_IMPL=v1, HMX_TILE_IMPL=v1, HMX_MOE_IMPL=v1 (first-generation kernels),
+ *   HMX_UPD_THREADS, HMX_UPD_MAXBLOCKS, HMX_STATIC_MAXBLOCKS, HMX_UPD_TPW, HMX_FUSED_FOLD=0, HMX_FOLD_IMPL=split,
+ *   HMX_OLDSUM_IMPL=gather|stream1, HMX_MOE_IMPL=v1 (first-generation kernels),
  *   HMX_DOT=f32 (tile kernels: fp32-MFMA distance GEMM only; default: the split-bf16 build wherever its LDS image fits -- same
  *   fp32 accuracy);
  *   host matrices (hmx_setup / hmx_get_matrix with HMX_HOST): HMX_XFER=pin (register the caller's buffer instead of moving it

@@ -495,7 +495,7 @@ def test_envelope_shapes(N, d, K, levels, nested):
 
 
 @pytest.mark.parametrize("env", [
-    {"HMX_UPDATE_IMPL": "v1", "HMX_TILE_IMPL": "v1", "HMX_MOE_IMPL": "v1"},   # first-generation cluster-lane VALU kernels
+    {"HMX_MOE_IMPL": "v1"},                                                   # first-generation ridge correction (k_moe_stats / k_moe_apply)
     {"HMX_FOLD_IMPL": "split"},                                               # k_fold + k_penalty instead of k_foldpen
     {"HMX_FUSED_FOLD": "0"},                                                  # separate k_foldpen launch per block step
     {"HMX_NREP": "1", "HMX_UPD_THREADS": "256", "HMX_UPD_MAXBLOCKS": "64", "HMX_UPD_TPW": "3"},   # launch geometry knobs

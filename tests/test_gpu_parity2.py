@@ -305,14 +305,14 @@ def test_every_cluster_tile_shape(K):
 
 
 # ---------------------------------------------------------------- k-means initialisation
-@pytest.mark.parametrize("env", [{}, {"HMX_TILE_IMPL": "v1"}])
-def test_kmeans_centers_headline_shape(monkeypatch, env):
-    """kmeans_centers (src/utils.cpp:10-64: seeding race + 10 Lloyd iterations) at d = 50, K = 100, 100k cells against the
-    oracle, on the MFMA tile kernels and on the cluster-lane fallbacks (k_seed_probe, k_lloyd)."""
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
-    Z, meta, _ = synth(100000, d=50, levels=(10,), seed=9)
-    skw, _ = prepare_setup_args(Z, meta, "cov0", nclust=100)
+@pytest.mark.parametrize("shape", [(100000, 50, 100), (20000, 128, 256)])
+def test_kmeans_centers_headline_shape(shape):
+    """kmeans_centers (src/utils.cpp:10-64: seeding race + 10 Lloyd iterations) against the oracle at the headline shape (d = 50,
+    K = 100, 100k cells: seeding and Lloyd on the MFMA tile kernel) and at the envelope's corner (d = 128, K = 256, 20k cells: the
+    K x d sum table does not fit beside the centroid image, Lloyd runs on k_lloyd)."""
+    N, d, K = shape
+    Z, meta, _ = synth(N, d=d, levels=(10,), seed=9)
+    skw, _ = prepare_setup_args(Z, meta, "cov0", nclust=K)
     g = Harmony(seed=17)
     g.setup(**skw)
     Yg = g.kmeans_centers()

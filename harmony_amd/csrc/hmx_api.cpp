@@ -5,6 +5,7 @@
 #include "../../include/harmony_mi355x_lab.h"      // (the reference interface + the probes / tuning declarations: the library defines both)
 #include "hmx_internal.h"
 #include "hmx_rrng.h"
+#include "hmx_plan.h"
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>
@@ -125,35 +126,34 @@ const char* hmx_last_warning(hmx_ctx* ctx) {   // one-shot: a warning is reporte
   return ctx->warn_ret.c_str();
 }
 
+// the round's Feistel network over [0, 4^half): half-width, mask and the six round keys (both directions share them)
+struct FeistelKeys {
+  int half; uint32_t mask, keys[6];
+  FeistelKeys(uint64_t seed, uint64_t round, uint64_t N) {
+    int bits = 2;
+    while (((uint64_t)1 << bits) < N) bits += 2;
+    half = bits / 2; mask = (uint32_t)(((uint64_t)1 << half) - 1);
+    for (int r = 0; r < 6; r++)
+      keys[r] = (uint32_t)(h_splitmix64(seed ^ (round * 0x9E3779B97F4A7C15ull) ^ ((uint64_t)(r + 1) << 56)) >> 32);
+  }
+};
 uint64_t hmx_feistel_cell(uint64_t seed, uint64_t round, uint64_t N, uint64_t pos) {
-  int bits = 2;
-  while (((uint64_t)1 << bits) < N) bits += 2;
-  const int half = bits / 2;
-  const uint32_t mask = (uint32_t)(((uint64_t)1 << half) - 1);
-  uint32_t keys[6];
-  for (int r = 0; r < 6; r++)
-    keys[r] = (uint32_t)(h_splitmix64(seed ^ (round * 0x9E3779B97F4A7C15ull) ^ ((uint64_t)(r + 1) << 56)) >> 32);
+  const FeistelKeys f(seed, round, N);
   uint64_t x = pos;
   do {
-    uint32_t L = (uint32_t)(x >> half), R = (uint32_t)(x & mask);
-    for (int r = 5; r >= 0; r--) { uint32_t t = R ^ (h_fmix32(L * 0x9E3779B1u + keys[r]) & mask); R = L; L = t; }
-    x = ((uint64_t)L << half) | R;
+    uint32_t L = (uint32_t)(x >> f.half), R = (uint32_t)(x & f.mask);
+    for (int r = 5; r >= 0; r--) { uint32_t t = R ^ (h_fmix32(L * 0x9E3779B1u + f.keys[r]) & f.mask); R = L; L = t; }
+    x = ((uint64_t)L << f.half) | R;
   } while (x >= N);
   return x;
 }
 uint64_t hmx_feistel_pos(uint64_t seed, uint64_t round, uint64_t N, uint64_t g) {
-  int bits = 2;
-  while (((uint64_t)1 << bits) < N) bits += 2;
-  const int half = bits / 2;
-  const uint32_t mask = (uint32_t)(((uint64_t)1 << half) - 1);
-  uint32_t keys[6];
-  for (int r = 0; r < 6; r++)
-    keys[r] = (uint32_t)(h_splitmix64(seed ^ (round * 0x9E3779B97F4A7C15ull) ^ ((uint64_t)(r + 1) << 56)) >> 32);
+  const FeistelKeys f(seed, round, N);
   uint64_t x = g;
   do {
-    uint32_t L = (uint32_t)(x >> half), R = (uint32_t)(x & mask);
-    for (int r = 0; r < 6; r++) { uint32_t t = L ^ (h_fmix32(R * 0x9E3779B1u + keys[r]) & mask); L = R; R = t; }
-    x = ((uint64_t)L << half) | R;
+    uint32_t L = (uint32_t)(x >> f.half), R = (uint32_t)(x & f.mask);
+    for (int r = 0; r < 6; r++) { uint32_t t = L ^ (h_fmix32(R * 0x9E3779B1u + f.keys[r]) & f.mask); L = R; R = t; }
+    x = ((uint64_t)L << f.half) | R;
   } while (x >= N);
   return x;
 }

@@ -167,6 +167,7 @@ int64_t hmx_get(hmx_ctx* ctx, const char* field, double* out, int64_t cap) {
     return scalar(1.0);
   }
   if (f == "chain") return scalar((ctx->chain_ok || ctx->D.chain_pair) ? 1.0 : 0.0);
+  if (f == "chain_wgs") return scalar((double)ctx->chain_wgs);      // workgroups of the chain: the device's compute units unless HMX_CHAIN_WGS says otherwise
   if (f == "chain_pair") return scalar(ctx->D.chain_pair ? 1.0 : 0.0);      // the wave-pair chain (k_tile MODE 6: 112 < K <= 224)
   if (f == "dot_bf") return scalar(ctx->D.dot_bf ? 1.0 : 0.0);     // split-bf16 tile kernels offered (each launch still checks its LDS budget)
   if (f == "sold_carry") return scalar(ctx->carry_ok ? 1.0 : 0.0);

@@ -1,0 +1,43 @@
+"""The plan tests/test_plan_cpu.py checks on the CPU IS the plan the library runs: for shapes the suite sets up elsewhere, the path flags of a
+live handle equal what the probe of harmony_amd/csrc/hmx_plan.h returns for the same shape and the device's real CU count."""
+import os
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from harmony_amd import Harmony, prepare_setup_args  # noqa: E402
+from helpers import synth  # noqa: E402
+from test_plan_cpu import plan  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+CASES = {                               # N, d, levels, K, sigma
+    "uniform_K50": (30000, 50, (2,), 50, 0.1),
+    "uniform_K100": (300000, 50, (10,), 100, 0.1),      # (20^2 blocks x 10 combinations x 64 <= N: old contributions carried, sort-free shuffle)
+    "K200_three_covariates": (120000, 50, (4, 10, 20), 200, 0.1),
+    "K_not_multiple_of_4": (20000, 30, (5,), 50 + 1, 0.1),
+    "sigma_vector": (6000, 30, (4,), 40, "vector"),
+}
+
+
+@pytest.mark.parametrize("name", sorted(CASES))
+def test_live_handle_runs_the_probed_plan(name, monkeypatch):
+    for k in [k for k in os.environ if k.startswith("HMX_")]:
+        monkeypatch.delenv(k)
+    N, d, levels, K, sigma = CASES[name]
+    Z, meta, _ = synth(N, d=d, levels=levels, seed=7)
+    skw, _ = prepare_setup_args(Z, meta, list(meta), nclust=K, sigma=np.linspace(0.08, 0.16, K) if sigma == "vector" else sigma)
+    h = Harmony(seed=1)
+    h.setup(**skw)                      # (no HMX_CHAIN_WGS: the chain's workgroup count "chain_wgs" is the device's CU count)
+    phi_i, phi_p, _, B = skw["Phi"]
+    C_ = len(levels)
+    combos, counts = np.unique(np.asarray(phi_i).reshape(N, C_), axis=0, return_counts=True)      # (one level per covariate and cell, grouped by covariate)
+    p = plan(N, K, d=d, B=int(B), C_=C_, Q=len(combos), nb=int(h._scalar("n_blocks")), cells_per_block=int(h._scalar("cells_per_block")),
+             cus=int(h._scalar("chain_wgs")), usig=int(sigma != "vector"), ntitems=int(((counts + 15) // 16).sum()))
+    live = {g: int(h._scalar(g)) for g in ("chain", "chain_pair", "dot_bf", "sold_carry", "shuffle_inv", "usig", "upd_wps")}
+    want = {"chain": int(p["chain_ok"] or p["chain_pair"]), "chain_pair": p["chain_pair"], "dot_bf": p["dot_bf"], "sold_carry": p["carry_ok"],
+            "shuffle_inv": p["shuf_inv"], "usig": p["usig"], "upd_wps": p["upd_wps"]}
+    print("PLAN", name, live)
+    assert live == want, (name, live, p)

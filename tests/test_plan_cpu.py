@@ -1,0 +1,140 @@
+"""The launch plan of hmx_setup (harmony_amd/csrc/hmx_plan.h) as a pure function: which path a shape takes, checked without a GPU.
+Every expected value below is derived from the expressions of the setup code the plan was lifted out of, with the derivation beside it."""
+import ctypes as C
+import os
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PLAN_SHAPE = ("N", "N_global", "d", "K", "B", "C", "Q", "nb", "cells_per_block", "world", "sharded", "cus", "usig", "ridge_arith", "oe_arith",
+              "obj_arith", "solve_arith", "tun_wps", "tun_tpw", "grid", "ntitems")
+PLAN_FIELDS = ("KP", "zs", "NCT", "NQ", "NT4", "tail", "NS", "NS2", "wNQ", "wNT4", "wtail", "wNS", "moe_mfma", "dot_bf", "usig", "rvec", "pen_lds",
+               "upd_wps", "upd_threads", "upd_maxblocks", "upd_tpw", "static_maxblocks", "oldsum_stream", "need_lorder", "nwmax", "objslots",
+               "r_store_always", "carry_ok", "qmask", "nkeys", "npad", "shuf_inv", "solve_on_device", "st_KH", "st_halves", "st_dma", "st_cpw", "st_nwg",
+               "fused_ok", "chain_ok", "chain_wgs", "chain_pair", "KH", "chain_folders", "chain_kw", "nrep", "upd_contig")
+_probe = []
+
+
+def plan_probe():
+    """tests/cpp/plan_probe.cpp built once per session with the host compiler (the header needs no HIP)"""
+    if not _probe:
+        import tempfile
+        so = os.path.join(tempfile.mkdtemp(prefix="plan_probe_"), "plan_probe.so")
+        subprocess.check_call([os.environ.get("CXX", "g++"), "-O1", "-std=c++17", "-fPIC", "-shared", os.path.join(ROOT, "tests", "cpp", "plan_probe.cpp"), "-o", so])
+        lib = C.CDLL(so)
+        lib.probe_plan.argtypes = [C.POINTER(C.c_longlong), C.POINTER(C.c_int), C.c_char_p, C.c_int]
+        _probe.append(lib)
+    return _probe[0]
+
+
+def plan(N, K, d=50, B=20, C_=1, Q=None, nb=20, **kw):
+    """the plan of one shape (the HMX_* switches come from the environment); a dict of PLAN_FIELDS, or {"limit": message}"""
+    s = dict(N=N, N_global=N, d=d, K=K, B=B, C=C_, Q=B if Q is None else Q, nb=nb, cells_per_block=max(1, N // nb), world=1, sharded=0, cus=256, usig=1,
+             ridge_arith=0, oe_arith=0, obj_arith=0, solve_arith=0, tun_wps=-1, tun_tpw=-1, grid=2048, ntitems=(N + 15) // 16)
+    assert not set(kw) - set(s), kw
+    s.update(kw)
+    out = (C.c_int * len(PLAN_FIELDS))()
+    msg = C.create_string_buffer(256)
+    if plan_probe().probe_plan((C.c_longlong * len(PLAN_SHAPE))(*[int(s[k]) for k in PLAN_SHAPE]), out, msg, 256):
+        return {"limit": msg.value.decode()}
+    return dict(zip(PLAN_FIELDS, out))
+
+
+@pytest.fixture(autouse=True)
+def no_switches(monkeypatch):
+    for k in [k for k in os.environ if k.startswith("HMX_")]:
+        monkeypatch.delenv(k)
+
+
+def diff(a, b):
+    return {k for k in a if a[k] != b[k]}
+
+
+# K = 100, 20 blocks, 256 CUs: the chain runs while N / 20 / 16 / (8 * 255) <= 20 tiles per resident wave, i.e. N <= 20 * 20 * 16 * 2040 = 13 056 000
+# (the quotient is exactly 20.0 there); one more tile per block is 20 * 16 = 320 more cells.
+CHAIN_N = 20 * 20 * 16 * 8 * 255
+# K = 200, B = 200, C = 3: KH = 100, folders of kw = ((200 + 11) / 12 + 3) & ~3 = 20 clusters -> F = 10; the pair chain runs while
+# N / 20 / 16 / (4 * (256 - 10)) <= 12 tiles per pair and block, i.e. N <= 12 * 984 * 16 * 20 = 3 778 560
+PAIR_N = 12 * 4 * (256 - 10) * 16 * 20
+C4 = dict(K=200, B=200, C_=3, Q=200)
+
+
+def test_chain_threshold_and_replicas(monkeypatch):
+    on, off = plan(CHAIN_N, 100), plan(CHAIN_N + 320, 100)
+    assert CHAIN_N == 13056000
+    assert (on["chain_ok"], on["fused_ok"], on["chain_pair"], on["chain_wgs"]) == (1, 1, 0, 256)
+    assert (off["chain_ok"], off["fused_ok"], off["chain_pair"]) == (0, 1, 0)
+    # replicas: 8 (8 * 20 * 100 entries are far below 2^20), 4 on the chain; contiguous tile ranges off the chain from 4 tiles per wave
+    assert (on["nrep"], off["nrep"], on["upd_contig"], off["upd_contig"]) == (4, 8, 0, 1)
+    assert diff(on, off) == {"chain_ok", "nrep", "upd_contig", "npad"}
+    monkeypatch.setenv("HMX_NREP", "8")
+    assert plan(CHAIN_N, 100)["nrep"] == 8 and plan(PAIR_N, **C4)["nrep"] == 8
+    monkeypatch.setenv("HMX_NREP", "2")
+    assert plan(CHAIN_N, 100)["nrep"] == 2 and plan(CHAIN_N + 320, 100)["nrep"] == 2
+
+
+def test_configs4_shape_takes_the_pair_chain_up_to_12_tiles():
+    on, off = plan(PAIR_N, **C4), plan(PAIR_N + 320, **C4)
+    assert PAIR_N == 3778560
+    # NCT = 13 > 7 cluster tiles: never the single-wave chain; 200 * 200 * 12 bytes of tables: no fold in the prologue either
+    assert (on["NCT"], on["chain_ok"], on["fused_ok"], off["chain_ok"], off["fused_ok"]) == (13, 0, 0, 0, 0)
+    assert (on["chain_pair"], on["KH"], on["chain_kw"], on["chain_folders"], on["nrep"], on["upd_contig"]) == (1, 100, 20, 10, 1, 0)
+    assert (off["chain_pair"], off["nrep"], off["upd_contig"]) == (0, 8, 1)          # (5.8 tiles per wave: contiguous ranges)
+    assert plan(5000000, **C4)["chain_pair"] == 0 and plan(1000000, **C4)["chain_pair"] == 1      # BASELINE configs[4] at 5M / 1M cells
+
+
+def test_carry_upd_wps_and_moe_mfma():
+    # carry: on iff nb^2 * Q * 64 <= N (nb <= 63, N + nb^2 * Q * 16 within int32, oe_arith off): 20^2 * 20 * 64 = 512 000
+    on, off = plan(512000, 100), plan(511999, 100)
+    assert (on["carry_ok"], on["qmask"], on["nkeys"], on["npad"]) == (1, 0x7FFFF, 400, 512000 + 400 * 20 * 16)
+    assert (off["carry_ok"], off["qmask"], off["nkeys"], off["npad"]) == (0, 0x7FFFFFFF, 20, 511999 + 20 * 20 * 16)
+    assert plan(512000, 100, oe_arith=1)["carry_ok"] == 0 and plan(64 * 64 * 64 * 20, 100, nb=64)["carry_ok"] == 0
+    assert (on["shuf_inv"], off["shuf_inv"], plan(512000, 100, world=2, sharded=1)["shuf_inv"]) == (1, 0, 0)
+    # four waves per SIMD iff uniform sigma and at most 4 cluster tiles (K <= 64)
+    for K, usig, wps in ((64, 1, 4), (50, 1, 4), (64, 0, 2), (80, 1, 2), (100, 1, 2)):
+        p = plan(100000, K, usig=usig)
+        assert (p["upd_wps"], p["upd_threads"], p["usig"]) == (wps, 1024 if wps == 4 else 512, usig), (K, usig)
+    # MFMA ridge kernels need K % 4 == 0 and d <= 64
+    assert [plan(100000, K, d=d)["moe_mfma"] for K, d in ((100, 50), (100, 64), (50, 50), (99, 50), (100, 68), (100, 100))] == [1, 1, 0, 0, 0, 0]
+    # split-bf16 distance GEMM: (NT4 > 4 or NS2 <= 2) and NS2 <= 4 -- rows of <= 64 PCs (two 32-PC steps) or of more than four 16-PC groups
+    # (d = 68: zs = 68, NT4 = 4, NS2 = 3 -> off; d = 80: NT4 = 5 -> on)
+    assert [plan(100000, 100, d=d)["dot_bf"] for d in (20, 50, 64, 68, 80, 100, 128)] == [1, 1, 1, 0, 1, 1, 1]
+
+
+def test_limits():
+    # centroid image: 4 quads x 50 PC steps x 1 KB at d = 200, K = 256 (beyond the envelope hmx_setup admits: its check comes first)
+    assert "centroid image" in plan(100000, 256, d=200)["limit"]
+    # padded order: 2e9 cells + 20 blocks x 500 000 combinations x 16 slots > 2 147 483 000 (no carry: 400 keys would not fit either)
+    assert "padded block order" in plan(2000000000, 100, Q=500000)["limit"]
+    assert plan(2000000000, 100, Q=20)["npad"] == 2000000000 + 400 * 20 * 16
+
+
+@pytest.mark.parametrize("env,shape,flips", [
+    ({"HMX_CHAIN": "0"}, dict(N=1000000, K=100), {"chain_ok": (1, 0), "nrep": (4, 8)}),
+    ({"HMX_CHAIN": "1"}, dict(N=CHAIN_N + 320, K=100), {"chain_ok": (0, 1), "nrep": (8, 4), "upd_contig": (1, 0)}),
+    ({"HMX_CHAIN": "1"}, dict(N=5000000, **C4), {"chain_pair": (0, 1), "nrep": (8, 1), "upd_contig": (1, 0)}),
+    ({"HMX_CHAIN": "0"}, dict(N=2500000, **C4), {"chain_pair": (1, 0), "nrep": (1, 8)}),
+    ({"HMX_CHAIN_PAIR": "0"}, dict(N=2500000, **C4), {"chain_pair": (1, 0), "nrep": (1, 8)}),
+    ({"HMX_CHAIN_PAIR": "1"}, dict(N=5000000, **C4), {"chain_pair": (0, 1), "nrep": (8, 1), "upd_contig": (1, 0)}),
+    ({"HMX_CHAIN_PAIR": "1"}, dict(N=1000000, K=100), {}),
+    ({"HMX_SOLD_CARRY": "0"}, dict(N=1000000, K=100), {"carry_ok": (1, 0), "qmask": (0x7FFFF, 0x7FFFFFFF), "nkeys": (400, 20), "npad": (1128000, 1006400), "shuf_inv": (1, 0)}),
+    ({"HMX_SOLD_CARRY": "1"}, dict(N=100000, K=100), {"carry_ok": (0, 1), "qmask": (0x7FFFFFFF, 0x7FFFF), "nkeys": (20, 400), "npad": (106400, 228000), "shuf_inv": (0, 1)}),
+    ({"HMX_DOT": "f32"}, dict(N=1000000, K=100), {"dot_bf": (1, 0)}),
+    ({"HMX_DOT": "f32"}, dict(N=1000000, **C4), {"dot_bf": (1, 0), "chain_pair": (1, 0), "nrep": (1, 8)}),      # (the pair chain exists in the split-bf16 build only)
+    ({"HMX_USIG": "0"}, dict(N=1000000, K=100), {"usig": (1, 0)}),
+    ({"HMX_USIG": "0"}, dict(N=1000000, K=64), {"usig": (1, 0), "upd_wps": (4, 2), "upd_threads": (1024, 512)}),
+    ({"HMX_MOE_STATS": "atomic"}, dict(N=1000000, K=100), {"st_dma": (1, 0), "st_cpw": (123, 0), "st_nwg": (509, 0)}),      # (62 500 tiles over 512 workgroups: 123 each)
+    ({"HMX_MOE_SOLVE": "host"}, dict(N=1000000, K=100), {"solve_on_device": (1, 0)}),
+    ({"HMX_SHUFFLE_INV": "0"}, dict(N=1000000, K=100), {"shuf_inv": (1, 0)}),
+    ({"HMX_SHUFFLE_INV": "2"}, dict(N=1000000, K=100), {}),
+    ({"HMX_SHUFFLE_INV": "2"}, dict(N=1000000, K=100, world=2, sharded=1), {"shuf_inv": (0, 1)}),
+    ({"HMX_FUSED_FOLD": "0"}, dict(N=CHAIN_N + 320, K=100), {"fused_ok": (1, 0)}),
+    ({"HMX_FUSED_FOLD": "0"}, dict(N=1000000, K=100), {"fused_ok": (1, 0), "chain_ok": (1, 0), "nrep": (4, 8)}),      # (the chain folds in its prologue)
+])
+def test_forcing_switch_flips_the_decision_it_documents(monkeypatch, env, shape, flips):
+    base = plan(**shape)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    forced = plan(**shape)
+    assert {k: (base[k], forced[k]) for k in diff(base, forced)} == flips

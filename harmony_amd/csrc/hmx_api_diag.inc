@@ -174,6 +174,11 @@ int64_t hmx_get(hmx_ctx* ctx, const char* field, double* out, int64_t cap) {
   if (f == "carried_rounds") return scalar((double)ctx->carried_rounds);
   if (f == "rounds_without_R") return scalar((double)ctx->rounds_without_R);
   if (f == "chain_rounds") return scalar((double)ctx->chain_rounds);
+  // further values of the launch plan (hmx_plan.h) as hmx_setup took them, for tests that claim a path
+  if (f == "need_lorder") return scalar((double)ctx->D.need_lorder);     // the shuffle also writes lorder / lcombo (k_oldsum's gather variant reads them)
+  if (f == "objslots") return scalar((double)ctx->D.objslots);           // slot rows of a round's objective partials: min(n_blocks, 64)
+  if (f == "upd_contig") return scalar((double)ctx->D.upd_contig);       // launch-per-step path: a wave owns a contiguous range of a block's tiles
+  if (f == "moe_mfma") return scalar((double)ctx->D.moe_mfma);           // MFMA ridge kernels (0: the first-generation ones)
   if (f == "shuffle_inv") return scalar(ctx->shuf_inv ? 1.0 : 0.0);
   if (f == "p2p:exchange_us") return scalar(ctx->p2p_exchange_us);
   if (f == "p2p:allreduce_calls") return scalar((double)ctx->p2p_ar_calls);

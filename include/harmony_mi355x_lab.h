@@ -30,6 +30,15 @@ extern "C" {
  *   through the process-wide ring of page-locked slots), HMX_XFER_THREADS (host threads that fill / drain the ring, default 8),
  *   HMX_PIN=0 (plain pageable copies).  INTEGRATION.md has the complete table of environment switches. */
 
+/* ---- further read-only scalar fields of hmx_get: the path hmx_setup chose and what the rounds did -------------------
+ * (the public header lists the reference's fields and "subset_clusters" "skipped_clusters" "n_combos" "usig" "upd_wps")
+ *   the launch plan (harmony_amd/csrc/hmx_plan.h), after hmx_setup: "n_blocks", "cells_per_block", "chain", "chain_pair", "chain_wgs", "dot_bf",
+ *   "sold_carry", "shuffle_inv", "need_lorder" (the shuffle also writes the cell / combination lists of the gathering old-contribution pass),
+ *   "objslots" (slot rows of a round's objective partials: min(n_blocks, 64)), "upd_contig" (launch-per-step path: contiguous tile ranges per
+ *   wave), "moe_mfma" (MFMA ridge kernels; 0: the first-generation ones);
+ *   counters since hmx_setup: "carried_rounds" (rounds whose old contributions came from the round before, no pass over R), "rounds_without_R"
+ *   (rounds whose R rows were not stored), "chain_rounds" (rounds run by a persistent chain). */
+
 /* probes of the R-compatible stream (host only, no device needed; used by the CPU tests) */
 void hmx_r_runif(uint32_t seed, int32_t n, double* out);            /* set.seed(seed); runif(n)                      */
 void hmx_r_shuffle(uint32_t seed, int64_t N, int64_t* out);         /* set.seed(seed); arma::shuffle(0..N-1)         */

@@ -1,6 +1,6 @@
 """Drive a handle (harmony_amd.Harmony or the CPU oracle) stage by stage and measure each stage against the fp64 spec (tests/stage_ref.py):
 before a stage the handle's own state is read through its getters, the spec applies the stage to it, and the result is compared with the
-handle's state after the stage.  Not a test module."""
+handle's state after the stage (run_stages); run_ladder does the same for the rounds of one clustering call.  Not a test module."""
 import numpy as np
 import scipy.sparse as sp
 
@@ -136,3 +136,53 @@ def run_stages(h, skw, Y0, order_of_round, stale_objective=True):
     _table_errs(h, R2, Phi, Pr_b, "cold", err)
     err["cold_obj"] = _obj_err(h, ref.objective(R2, dist2, h.O, h.E, Phi, sigma, theta, N))
     return err, info
+
+
+def run_ladder(make_handle, skw, Y0, order_of_round, rounds=5, probe=None):
+    """What a round hands to the next one.  For m = 1..rounds a fresh handle H_m (make_handle(): the same setup and seed every time) runs
+    init_cluster_cpp(Y0) and ONE cluster_cpp of m rounds (the caller's options keep the windowed check from ending it: kmeans_rounds[-1] == m
+    is asserted); R_0 is the R after init, R_j the R H_j ends on.  Rung m is the spec of round m - 1, teacher-forced from R_{m-1} to H_m's own
+    R_m: H_m's first m - 1 rounds are judged through the state they left for its last one -- wrong carried sums, a row read that was never
+    stored or a wrong sort set of round m - 1 move R_m off the spec.  (H_m's unstored R_{m-1} is H_{m-1}'s stored one if the library repeats
+    itself from run to run: the caller compares rung["first"] between the rungs.)
+    order_of_round(h, r): the update order of round r (pushing it into the handle first if the orders are injected; called for every round
+    of the call before cluster_cpp).  probe(h): counters of the handle, kept as rung["probe"].
+    Returns the rungs: {"m", "R", "argmax", "O", "E", "obj" (the worst of H_m's m round entries against the spec terms on R_1 .. R_m, the
+    distances those of the head, the tables those of H_j), "first" (H_m's first round entry: total and the three terms), "probe"}."""
+    Phi = phi_matrix(skw["Phi"])
+    sigma = np.asarray(skw["sigma"], dtype=np.float64)
+    theta = np.asarray(skw["theta"], dtype=np.float64)
+    N = Phi.shape[1]
+    nb, cpb, _ = ref.block_partition(N, skw["block_size"])
+    rungs, obj_spec = [], []
+    R_prev = Y = Zc0 = dist0 = Pr_b = None
+    for m in range(1, rounds + 1):
+        h = make_handle()
+        if m == 1:
+            Pr_b = np.asarray(h.Pr_b)
+            Zc0 = h.getZcorr()
+        h.init_cluster_cpp(Y0)
+        if m == 1:
+            Y = h.Y
+            R_prev = h.R
+            dist0 = ref.head(Y, Zc0, sigma, Phi, Pr_b)[1]
+        h.max_iter_kmeans = m
+        orders = [order_of_round(h, r) for r in range(m)]
+        assert h.cluster_cpp() == 0
+        assert int(h.kmeans_rounds[-1]) == m, (m, h.kmeans_rounds)
+        R_m = h.R
+        Rs = ref.update_round(R_prev, R_m, Y, Zc0, Phi, Pr_b, sigma, theta, orders[m - 1], nb, cpb)
+        rung = {"m": m, "R": float(np.abs(R_m - Rs).max()), "argmax": _argmax_clear(R_m, Rs)}
+        del Rs, orders
+        _table_errs(h, R_m, Phi, Pr_b, "tab", rung)
+        rung["O"], rung["E"] = rung.pop("tab_O"), rung.pop("tab_E")
+        obj_spec.append(np.asarray(ref.objective(R_m, dist0, h.O, h.E, Phi, sigma, theta, N)))
+        got = np.stack([h.objective_kmeans_dist, h.objective_kmeans_entropy, h.objective_kmeans_cross], axis=1)
+        assert got.shape[0] == m + 1, got.shape            # the head's entry and one per round
+        rung["obj"] = max(float(np.max(np.abs(got[1 + j] - obj_spec[j])) / np.sum(np.abs(obj_spec[j]))) for j in range(m))
+        rung["first"] = [float(h.objective_kmeans[1])] + [float(v) for v in got[1]]
+        rung["probe"] = probe(h) if probe else None
+        rungs.append(rung)
+        R_prev = R_m
+        del h
+    return rungs

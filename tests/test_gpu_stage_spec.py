@@ -1,6 +1,10 @@
 """Each stage of the HIP path against the fp64 spec (tests/stage_ref.py) across the dispatch envelope: init, one clustering round
 (teacher-forced), the ridge correction, a stand-alone objective after it and the next call's cold start.  Both sides start from the
-handle's own state, so nothing drifts and the bars sit near fp32 rounding.  Every case asserts the path it claims through the getters."""
+handle's own state, so nothing drifts and the bars sit near fp32 rounding.  Every case asserts the path it claims through the getters.
+The o_ .. r_ cases walk the branches of the launch plan (harmony_amd/csrc/hmx_plan.h) on the block count -- 63 | 64 | 65 | 100 | 1000 blocks --, the
+d window 65..76 and the launch geometry switches; tests/test_stage_ref_cpu.py holds their claimed paths to the plan itself, without a GPU.
+The round ladder (run_ladder) judges what a round hands to the next one -- carried old contributions, elided R stores, the 4-round sort
+groups -- against the same spec."""
 import json
 import os
 import sys
@@ -16,12 +20,13 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 from harmony_amd import Harmony, harmony_options, prepare_setup_args  # noqa: E402
 from helpers import synth  # noqa: E402
 from oracle.oracle import feistel_order  # noqa: E402
-from stage_check import run_stages  # noqa: E402
+from stage_check import run_ladder, run_stages  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 # Bars: at most 10x the worst error measured over these cases on an MI355X (in brackets).  Both sides share the fp32 inputs; what is left is
-# the library's own fp32 rounding.
+# the library's own fp32 rounding.  The o_ .. r_ cases and the round ladders stay below the a_ .. n_ figures in every column (d = 68 / 76: R 3.7e-6 /
+# 3.9e-6 under R_d128; the ladders' rungs: R 2.0e-6 .. 2.3e-6, tables 2.8e-8, objective 1.2e-7 .. 2.7e-7): no bar was added or moved for them.
 BARS = {
     "R": 5e-6,          # teacher-forced R, max-abs, d <= 64 [2.7e-6]
     "R_d128": 1e-5,     # ... d = 128: dist sums more than twice as many fp32 products, and R moves by R (1 - R) ddist / sigma [5.1e-6]
@@ -54,9 +59,12 @@ def _skipped_population(N, d, seed):
     return Z, {"cov0": lev}
 
 
-def _case(name):
-    """(Z, meta, vars_use, setup kwargs, environment, handle seed, path assertions)"""
+def _case(name, cus=256):
+    """(Z, meta, vars_use, setup kwargs, environment, handle seed, path assertions); cus: compute units of the device (one case sizes itself by it)"""
     o = {}
+    if name.endswith("_pushed") and name[:-7] in PUSHED:      # the same case under host-injected orders (prepare_round's pos / cells_per_block path)
+        Z, meta, var, kw, env, seed, path = _case(name[:-7], cus)
+        return Z, meta, var, kw, env, seed, dict(path, push=1)
     if name == "a_chain_schur":
         Z, meta, _ = synth(100000, d=50, levels=(10,), seed=1)
         return Z, meta, "cov0", dict(nclust=100), o, 3, dict(chain=1, chain_pair=0, usig=1, upd_wps=2, host=0, min_kept=8)
@@ -107,18 +115,71 @@ def _case(name):
     if name == "n_baseline_1M":
         Z, meta, _ = synth(1000000, d=50, levels=(10,), seed=17)
         return Z, meta, "cov0", dict(nclust=100), o, 17, dict(chain=1, host=0)
+    # ---- the block count against the plan's thresholds: nb <= 63 (carry, 6-bit block fields of lpair), nb < 64 (sort-free shuffle), nb <= 64 (chains),
+    #      objslots = min(nb, 64) (above it k_tile adds into slot row j % objslots), need_lorder = nb * K * 8 > 64 KB
+    if name == "o_blocks_100":
+        Z, meta, _ = synth(40000, d=50, levels=(10,), seed=18)
+        return Z, meta, "cov0", dict(nclust=100, options=harmony_options(block_size=0.01)), o, 18, dict(
+            n_blocks=100, cells_per_block=400, chain=0, sold_carry=0, shuffle_inv=0, need_lorder=1, objslots=64, host=0)
+    if name == "o_blocks_63_carried":       # the last block index that fits lpair's 6 bits
+        Z, meta, _ = synth(80000, d=50, levels=(4,), seed=19)
+        return Z, meta, "cov0", dict(nclust=100, options=harmony_options(block_size=0.016)), {"HMX_SOLD_CARRY": "1"}, 19, dict(
+            n_blocks=63, chain=1, sold_carry=1, shuffle_inv=1, objslots=63, host=0)
+    if name == "o_blocks_64":
+        Z, meta, _ = synth(40000, d=50, levels=(10,), seed=20)
+        return Z, meta, "cov0", dict(nclust=100, options=harmony_options(block_size=1.0 / 64)), o, 20, dict(
+            n_blocks=64, cells_per_block=625, chain=1, sold_carry=0, shuffle_inv=0, host=0)
+    if name == "o_blocks_65":               # objslots < n_blocks: block 64 adds into block 0's slot row
+        Z, meta, _ = synth(40000, d=50, levels=(10,), seed=21)
+        return Z, meta, "cov0", dict(nclust=100, options=harmony_options(block_size=0.0155)), o, 21, dict(
+            n_blocks=65, cells_per_block=620, last_block=320, chain=0, objslots=64, host=0)
+    if name == "o_blocks_1000_four_waves":  # blocks of two 16-cell tiles spread over 6 combinations
+        Z, meta, _ = synth(30000, d=50, levels=(6,), seed=22)
+        return Z, meta, "cov0", dict(nclust=48, options=harmony_options(block_size=0.001)), o, 22, dict(
+            n_blocks=1000, cells_per_block=30, upd_wps=4, chain=0, need_lorder=1, host=0)
+    if name == "p_contiguous_ranges":       # launch-per-step path, one block: from 4 tiles per wave a wave owns a contiguous range (4.29 here)
+        N = 140000 if cus == 256 else int(4.29 * 16 * 8 * (cus - 1)) // 16 * 16
+        Z, meta, _ = synth(N, d=50, levels=(10,), seed=23)
+        return Z, meta, "cov0", dict(nclust=100, options=harmony_options(block_size=1.0)), {"HMX_CHAIN": "0"}, 23, dict(
+            chain=0, upd_contig=1, host=0)
+    # ---- 64 < d <= 76: zs 68..76, NT4 = 4, NS2 = 3: the fp32 register form of the distance GEMM on rows longer than 64 PCs, on the chain,
+    #      with the first-generation ridge kernels (d > 64)
+    if name in ("q_d68_fp32_on_the_chain", "q_d76_fp32_on_the_chain"):
+        d = int(name[3:5])
+        Z, meta, _ = synth(30000, d=d, levels=(10,), seed=24 + d)
+        return Z, meta, "cov0", dict(nclust=100), o, 24, dict(dot_bf=0, chain=1, moe_mfma=0, host=0)
+    if name == "r_launch_geometry":
+        Z, meta, _ = synth(30000, d=50, levels=(10,), seed=25)
+        env = {"HMX_NREP": "1", "HMX_UPD_THREADS": "256", "HMX_UPD_MAXBLOCKS": "64", "HMX_UPD_TPW": "3", "HMX_CHAIN": "0"}
+        return Z, meta, "cov0", dict(nclust=100), env, 25, dict(chain=0, host=0)
     raise KeyError(name)
 
 
 CASES = ["a_chain_schur", "b_four_waves_dense", "c_first_generation_k30_d17", "c_first_generation_k256_d128", "d_wave_pair_nested_subset",
          "e_launch_per_step_k152", "f_host_closed_form_1200", "g_host_cholesky_1200x3", "h_device_1100", "i_crossed_small_combinations",
          "j_skipped", "k_fixed_lambda_sigma_theta0", "l_forced_fallbacks", "m_block_0.3_prime_pushed", "m_block_1.0", "n_baseline_1M"]
+PLAN_CASES = ["o_blocks_100", "o_blocks_63_carried", "o_blocks_64", "o_blocks_65", "o_blocks_1000_four_waves", "p_contiguous_ranges",
+              "q_d68_fp32_on_the_chain", "q_d76_fp32_on_the_chain", "r_launch_geometry"]
+PUSHED = ["o_blocks_100", "o_blocks_65", "o_blocks_1000_four_waves"]
+CASES += PLAN_CASES + [n + "_pushed" for n in PUSHED]
+# the getters a case may claim (hmx_get scalars)
+PATH_GETTERS = ("chain", "chain_pair", "usig", "upd_wps", "dot_bf", "sold_carry", "shuffle_inv", "need_lorder", "objslots", "upd_contig", "moe_mfma",
+                "n_blocks", "cells_per_block")
+
+
+def _device_cus():
+    """compute units of the device, as the library's plan sees them: the chain's workgroups of a small fit (one per CU unless HMX_CHAIN_WGS says otherwise)"""
+    Z, meta, _ = synth(2000, d=20, levels=(2,), seed=1)
+    skw, _ = prepare_setup_args(Z, meta, "cov0", nclust=8)
+    h = Harmony(seed=1)
+    h.setup(**skw)
+    return int(h._scalar("chain_wgs"))
 
 
 @pytest.mark.parametrize("name", CASES)
 def test_stages_match_the_spec(name, monkeypatch):
     t0 = time.time()
-    Z, meta, var, kw, env, seed, path = _case(name)
+    Z, meta, var, kw, env, seed, path = _case(name, _device_cus() if name == "p_contiguous_ranges" else 256)      # (the one case sized by the CU count)
     for k, v in env.items():
         monkeypatch.setenv(k, v)
     skw, _ = prepare_setup_args(Z, meta, var, **kw)
@@ -142,9 +203,11 @@ def test_stages_match_the_spec(name, monkeypatch):
     msg = repr((name, err, info))
 
     # the path this case claims
-    for g in ("chain", "chain_pair", "usig", "upd_wps", "dot_bf", "sold_carry"):
+    for g in PATH_GETTERS:
         if g in path:
             assert int(h._scalar(g)) == path[g], (g, msg)
+    if "last_block" in path:
+        assert N - (path["n_blocks"] - 1) * path["cells_per_block"] == path["last_block"], msg
     if path["host"]:
         assert h.timer("moe_solve_host") > 0, msg
     else:
@@ -173,3 +236,76 @@ def test_stages_match_the_spec(name, monkeypatch):
     assert err["W"] <= BARS["W"], msg
     assert err["Lambda"] <= BARS["Lambda"], msg
     assert (info["subset_h"], info["skipped_h"]) == (info["subset"], info["skipped"]), msg
+
+
+# ---- the round ladder: what a round hands to the next one (stage_check.run_ladder) --------------------------------------------------------
+# name -> (cells, clusters, levels, nested, environment, seed, the path it claims)
+LADDERS = {
+    # the carry pays by itself: 400 keys x 10 combinations x 64 <= N
+    "chain": (300000, 100, (10,), False, {}, 31, dict(chain=1, chain_pair=0, sold_carry=1)),
+    "launch_per_step": (300000, 100, (10,), False, {"HMX_CHAIN": "0"}, 31, dict(chain=0, chain_pair=0, sold_carry=1)),
+    "wave_pair_chain": (60000, 200, (8, 64, 128), True, {"HMX_SOLD_CARRY": "1"}, 32, dict(chain=1, chain_pair=1, sold_carry=1)),
+}
+LADDER_ROUNDS = 5       # rounds 0..3 are one sort group, round 4 opens the next
+
+
+def _ladder(name):
+    """(Z, meta, vars_use, setup kwargs, environment, seed, path); epsilon_cluster = -1e9: the windowed check (iter > window_size) never ends a call"""
+    N, K, levels, nested, env, seed, path = LADDERS[name]
+    Z, meta, _ = synth(N, d=50, levels=levels, nested=nested, seed=seed)
+    return Z, meta, ["cov%d" % i for i in range(len(levels))], dict(nclust=K, options=harmony_options(epsilon_cluster=-1e9)), env, seed, path
+
+
+@pytest.mark.parametrize("name", sorted(LADDERS))
+def test_round_ladder_matches_the_spec(name, monkeypatch):
+    """H_m, m = 1..5: one cluster_cpp of m rounds from the same setup, seed and Y0; rung m = round m - 1 of H_m against the fp64 spec, from
+    H_{m-1}'s stored R to H_m's own.  The counters must show that the rounds before the last really took the path under test.  Every one of
+    the m rounds took its old contributions from sums filed before it, none from a pass over R: round 0 from init_cluster_cpp's head
+    (head_pass files them, Dev::head_gather), rounds 1 .. m - 1 from the round before (Sold_next) -- carried_rounds == m, of which H_1's single
+    one is the head's, so m - 1 come from a round.  min(m - 1, 4) rounds stored no R: only a round that wrote the next round's sums may elide
+    its stores, and a round that the windowed check could end stores them (from the fifth on).  A dead carry reads 1 / 0 there and fails
+    here instead of passing on the fresh-pass path.
+    Run to run: DESIGN 3 item 5 (exact integer tables, independent of the atomics' order) and 4.5 (elided stores: bit-identical results)
+    document this path as bit-reproducible, so every H_m's first round entry is asserted BITWISE equal to H_1's only one."""
+    t0 = time.time()
+    Z, meta, var, kw, env, seed, path = _ladder(name)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    skw, _ = prepare_setup_args(Z, meta, var, **kw)
+    del Z
+
+    def make_handle():
+        h = Harmony(seed=seed)
+        h.setup(**skw)
+        return h
+
+    h = make_handle()
+    N = int(h.N)
+    Y0 = h.kmeans_centers()
+    del h
+    orders = {}
+
+    def order_of_round(h, r):
+        if r not in orders:
+            orders[r] = feistel_order(seed, r, N)
+        return orders[r]
+
+    def probe(h):
+        return {g: int(h._scalar(g)) for g in ("carried_rounds", "rounds_without_R", "chain_rounds", "chain", "chain_pair", "sold_carry", "shuffle_inv")}
+
+    rungs = run_ladder(make_handle, skw, Y0, order_of_round, rounds=LADDER_ROUNDS, probe=probe)
+    for rung in rungs:
+        print("STAGE_SPEC", "ladder_%s_rung_%d" % (name, rung["m"]), json.dumps({"err": rung, "seconds": round(time.time() - t0, 1)}, default=str))
+    for rung in rungs:
+        m, p, msg = rung["m"], rung["probe"], repr((name, rung))
+        for g in ("chain", "chain_pair", "sold_carry"):
+            assert p[g] == path[g], (g, msg)
+        assert p["carried_rounds"] == m, ("rounds that took their old contributions from the pass before them (the head, then m - 1 rounds)", msg)
+        assert p["carried_rounds"] - rungs[0]["probe"]["carried_rounds"] == m - 1, ("rounds that took their old contributions from the round before", msg)
+        assert p["rounds_without_R"] == min(m - 1, 4), ("rounds that stored no R", msg)
+        assert p["chain_rounds"] == (m if path["chain"] else 0), msg
+        assert rung["R"] <= BARS["R"], msg
+        assert rung["argmax"] == 0, msg
+        assert rung["O"] <= BARS["tab"] and rung["E"] <= BARS["tab"], msg
+        assert rung["obj"] <= BARS["obj"], msg
+        assert rung["first"] == rungs[0]["first"], ("round 0 of H_%d is not round 0 of H_1 bit for bit" % m, msg, rungs[0]["first"])

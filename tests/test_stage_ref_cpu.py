@@ -14,7 +14,10 @@ import stage_ref as ref  # noqa: E402
 from harmony_amd import harmony_options, prepare_setup_args  # noqa: E402
 from helpers import synth  # noqa: E402
 from oracle.oracle import OracleHarmony  # noqa: E402
-from stage_check import phi_matrix, run_stages  # noqa: E402
+from oracle.oracle import feistel_order  # noqa: E402
+from stage_check import phi_matrix, run_ladder, run_stages  # noqa: E402
+from test_gpu_stage_spec import LADDERS, PLAN_CASES, _case, _ladder  # noqa: E402  (the GPU cases: their claims are checked here first)
+from test_plan_cpu import plan  # noqa: E402
 
 BAR = 1e-5      # the oracle keeps R, O, E, Z, Y in fp32
 
@@ -43,6 +46,10 @@ CASES = _cases()
 @pytest.mark.parametrize("name", sorted(CASES))
 def test_oracle_stages_match_the_spec(name):
     Z, meta, var, kw = CASES[name]
+    _oracle_stages(name, Z, meta, var, kw)
+
+
+def _oracle_stages(name, Z, meta, var, kw):
     skw, _ = prepare_setup_args(Z, meta, var, **kw)
     h = OracleHarmony(accurate=True, seed=1)
     h.setup(**skw)
@@ -104,6 +111,12 @@ def test_block_partition_follows_the_fp32_formula():
     nb, cpb, bounds = ref.block_partition(100003, 0.05)
     assert (nb, cpb) == (20, 5000) and bounds[-1] == (95000, 100003)
     assert sum(hi - lo for lo, hi in bounds) == 100003
+    # the block sizes of the many-block GPU cases at their N: (n_blocks, cells_per_block, cells of the last block)
+    for N, bs, want in ((40000, 0.01, (100, 400, 400)), (80000, 0.016, (63, 1280, 640)), (60000, 0.016, (63, 960, 480)), (40000, 1.0 / 64, (64, 625, 625)),
+                        (40000, 0.0155, (65, 620, 320)), (30000, 0.001, (1000, 30, 30))):
+        nb, cpb, bounds = ref.block_partition(N, bs)
+        assert (nb, cpb, bounds[-1][1] - bounds[-1][0]) == want, (N, bs)
+        assert len(bounds) == nb and bounds[-1][1] == N and sum(hi - lo for lo, hi in bounds) == N
 
 
 @pytest.mark.parametrize("levels,lam,cutoff", [((4,), None, 1e-5), ((4,), "fixed", 0.2), ((3, 5), None, 0.15), ((2, 3, 4), "fixed", 1e-5)])
@@ -121,3 +134,88 @@ def test_combination_sums_equal_the_per_cell_products(levels, lam, cutoff):
     assert np.abs(s["W"] - Wd).max() <= 1e-12 * max(1.0, np.abs(Wd).max())
     if cutoff > 1e-3:
         assert s["subset"].any()
+
+
+# ---- the many-block / d 65..76 / launch-geometry cases of tests/test_gpu_stage_spec.py, before a GPU sees them ------------------------------
+def _design(skw):
+    """(B, C, Q, ntitems) of a setup: levels, covariates, level combinations present, 16-cell tiles with every combination's cells in tiles of its own"""
+    Phi = phi_matrix(skw["Phi"])
+    q_of, levels = ref._combinations(Phi, skw["B_vec"])
+    return Phi.shape[0], len(skw["B_vec"]), levels.shape[0], int(sum((n + 15) // 16 for n in np.bincount(q_of)))
+
+
+def _plan_of(skw, env, monkeypatch):
+    """the launch plan hmx_setup would take at 256 CUs: as the handle's getters report it"""
+    for k in [k for k in os.environ if k.startswith("HMX_")]:
+        monkeypatch.delenv(k)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    B, C, Q, ntitems = _design(skw)
+    d, N = skw["Z"].shape
+    nb, cpb, _ = ref.block_partition(N, skw["block_size"])
+    p = plan(N, skw["K"], d=d, B=B, C_=C, Q=Q, nb=nb, cells_per_block=cpb, ntitems=ntitems, usig=int(np.ptp(skw["sigma"]) == 0))
+    assert "limit" not in p, p
+    p.update(chain=int(p["chain_ok"] or p["chain_pair"]), sold_carry=p["carry_ok"], shuffle_inv=p["shuf_inv"], n_blocks=nb, cells_per_block=cpb)
+    return p, Q
+
+
+@pytest.mark.parametrize("name", PLAN_CASES)
+def test_gpu_cases_claim_what_the_plan_gives(name, monkeypatch):
+    """a later change of a threshold must not silently empty a case: its claimed path is the plan's, for its own B, Q and tile count"""
+    Z, meta, var, kw, env, _seed, path = _case(name)
+    skw, _ = prepare_setup_args(Z, meta, var, **kw)
+    p, Q = _plan_of(skw, env, monkeypatch)
+    N = Z.shape[0]
+    claims = {g: v for g, v in path.items() if g not in ("host", "push", "last_block")}
+    assert {g: p[g] for g in claims} == claims
+    assert p["solve_on_device"] == 1 - path["host"]
+    if "last_block" in path:
+        assert N - (p["n_blocks"] - 1) * p["cells_per_block"] == path["last_block"]
+    if name == "o_blocks_63_carried":
+        # the padded order with 63 * 63 keys stays inside int32, and the blocks inside lpair's 6 bits
+        assert (p["nkeys"], p["npad"]) == (3969, N + 3969 * Q * 16) and p["npad"] < 2 ** 31 and p["n_blocks"] - 1 < 64
+    if name == "o_blocks_1000_four_waves":
+        assert p["cells_per_block"] <= 32 and Q == 6          # two 16-cell tiles over six combinations
+    if name == "p_contiguous_ranges":
+        assert 4.0 <= N / 16 / (8 * 255) < 4.5
+    if name.startswith("q_d"):
+        assert (p["NT4"], p["NS2"], p["chain_ok"]) == (4, 3, 1) and 68 <= p["zs"] <= 76
+    if name == "r_launch_geometry":
+        assert (p["nrep"], p["upd_threads"], p["upd_maxblocks"], p["upd_tpw"]) == (1, 256, 64, 3)
+
+
+@pytest.mark.parametrize("name", sorted(LADDERS))
+def test_gpu_ladders_claim_what_the_plan_gives(name, monkeypatch):
+    Z, meta, var, kw, env, _seed, path = _ladder(name)
+    skw, _ = prepare_setup_args(Z, meta, var, **kw)
+    p, _Q = _plan_of(skw, env, monkeypatch)
+    assert {g: p[g] for g in path} == path
+    assert skw["epsilon_kmeans"] < -1e8         # the windowed check never ends a call
+
+
+@pytest.mark.parametrize("name", ["o_blocks_100", "o_blocks_64", "o_blocks_65", "o_blocks_1000_four_waves", "q_d68_fp32_on_the_chain",
+                                  "q_d76_fp32_on_the_chain"])
+def test_oracle_stages_match_the_spec_on_the_small_gpu_cases(name):
+    """the small new GPU cases through the CPU oracle: the spec handles 63..1000 blocks and d = 68 / 76, and the cases' keep decisions sit away
+    from the cutoff because of their data (everything they depend on but the library's own fp32 tables)"""
+    Z, meta, var, kw, _env, _seed, _path = _case(name)
+    _oracle_stages(name, Z, meta, var, kw)
+
+
+def test_oracle_round_ladder_matches_the_spec():
+    """the ladder's spec on the oracle (five rounds in one call, the documented generator's orders) before it judges a kernel"""
+    Z, meta, _ = synth(3000, d=20, levels=(3,), seed=6)
+    skw, _ = prepare_setup_args(Z, meta, "cov0", nclust=12, options=harmony_options(epsilon_cluster=-1e9))
+    seed = 5
+    Y0 = skw["Z"][:, np.random.default_rng(12).choice(3000, 12, replace=False)]
+
+    def make_handle():
+        h = OracleHarmony(accurate=True, seed=seed)
+        h.setup(**skw)
+        return h
+
+    rungs = run_ladder(make_handle, skw, Y0, lambda h, r: feistel_order(seed, r, 3000), rounds=5)
+    assert [r["m"] for r in rungs] == [1, 2, 3, 4, 5]
+    for r in rungs:
+        assert r["R"] <= BAR and r["argmax"] == 0 and max(r["O"], r["E"], r["obj"]) <= BAR, r
+        assert r["first"] == rungs[0]["first"], r      # the oracle repeats itself bit for bit

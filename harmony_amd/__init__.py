@@ -6,9 +6,10 @@ object) over the C ABI in include/harmony_mi355x.h.  All numerics run in hand-wr
 """
 from .harmony_obj import Harmony, HarmonyError
 from .mapping import HarmonyReference, map_query
+from .metrics import compute_lisi, knn, knn_predict, lisi_from_knn
 from .options import harmony_options
 from .ui import RunHarmony, prepare_setup_args
 from .utils import harmonize
 
 __all__ = ["RunHarmony", "harmony_options", "Harmony", "HarmonyError", "harmonize", "prepare_setup_args", "map_query",
-           "HarmonyReference"]
+           "HarmonyReference", "knn", "compute_lisi", "lisi_from_knn", "knn_predict"]

@@ -64,6 +64,15 @@ SIGNATURES = {
     "hmx_debug_seq_arr": (C.c_int, [C.POINTER(C.c_float), C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float), _lp, _dp]),
 }
 
+# every symbol include/harmony_mi355x_metrics.h declares (kNN, LISI): kept apart from the reference interface above
+_fp = C.POINTER(C.c_float)
+METRICS_SIGNATURES = {
+    "hmx_knn": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int64,
+                          C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]),
+    "hmx_lisi": (C.c_int, [C.c_void_p, _ip, _fp, C.c_int64, C.c_int32, _ip, C.c_int64, C.c_int32, _ip, C.c_double, _dp]),
+    "hmx_compute_lisi": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32, _ip, C.c_int32, _ip, C.c_double, _dp]),
+}
+
 _lib = None
 
 
@@ -81,7 +90,7 @@ def load():
             "libharmony_mi355x.so is not built (%s). Run `python -m harmony_amd.build`; "
             "harmony_amd has no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(METRICS_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the ABI and the header drift apart
         fn.restype = res
         fn.argtypes = args

@@ -325,7 +325,23 @@ void l_query_stats(const Launch& L, const QueryDev& Q, int summary);
 void l_query_fold(const Launch& L, const double* part, const int* qchunk, int nq, int total, double* out);
 void l_query_apply(const Launch& L, const QueryDev& Q);
 
-// ---- reference arithmetic: restarted sequential fp32 sums (hmx_seq.hip) ------------------------------------------------------------
+// ---- integration metrics: exact kNN and LISI (hmx_knn.hip) ------------------------------------------------------------------------------
+constexpr int KNN_QROWS = 64;              // query rows per workgroup (16 per wave)
+constexpr int KNN_SLAB = 64;               // data rows staged per step
+struct KnnDev {
+  const float* X; const float* xn; long long N;      // data rows [N][zs] (pads 0) and their squared norms
+  const float* Q; const float* qn; long long Nq;     // query rows, likewise (the data rows themselves in self-exclusion mode)
+  int zs, NG, k, excl;                               // row stride, PC groups of 16, neighbours, 1: row i never returns index i
+  long long chunk; int nchunks;                      // data rows per chunk (a multiple of KNN_SLAB), chunks = grid.y
+  unsigned long long* part;                          // [Nq][nchunks][k] the chunks' sorted keys (nchunks > 1)
+  int* idx; float* dist;                             // [Nq][k] result
+};
+void l_knn_ingest(const Launch& L, const void* src, int f32, long long n, int d, int zs, float* dst, float* nrm);
+void l_knn(const Launch& L, const KnnDev& P);
+void l_lisi(const Launch& L, const int* idx, const float* dist, long long Nq, int m, const int* labels, long long N, int ncols, double perplexity,
+            double* out);
+
+// ---- reference arithmetic: restarted sequential fp32 sums (hmx_seq.hip)------------------------------------------------------------
 struct SeqSeg { int off; int cnt; };       // a segment of a chain: cells list[off .. off + cnt) (or the cells off .. off + cnt - 1 themselves)
 struct SeqChain { int seg0; int nseg; };   // the segments of one chain, in chain order
 // (conv_zero: the two statistics words the scan behind this pass will add to -- zeroed by the pass itself, no memset launch; or nullptr)

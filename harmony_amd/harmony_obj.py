@@ -286,6 +286,12 @@ class Harmony(object):
             raise HarmonyError("get_matrix(%s) failed: %s" % (field, self._lib.hmx_last_error(self._h).decode()))
         return out
 
+    def lisi(self, meta_data, label_colnames, perplexity=30):
+        """LISI (metrics.compute_lisi) of the handle's current Z_corr over the named columns of meta_data, one label per cell in the order the
+        cells were given in: N x len(label_colnames).  Z_corr is read where it lives in HBM; no host round trip."""
+        from .metrics import harmony_lisi
+        return harmony_lisi(self, meta_data, label_colnames, perplexity)
+
     def getZorig(self):
         return self._get("Z_orig", (int(self.d), int(self._scalar("N_local"))))
 

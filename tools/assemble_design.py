@@ -96,6 +96,15 @@ try:
 except Exception as e:       # noqa: BLE001
     missing.append("scaling_prediction.py: %s" % e)
 
+lb = line("r7_lisi_bench.json")      # tools/lisi_bench.py
+if lb:
+    kt = "; ".join("%s %.1f ms" % (k["kernel"].split("(")[0].replace("void hmx::", ""), k["total_ms"]) for k in lb.get("kernel_trace", []))
+    vals["LISI_MEASURED"] = ("**Measured** (`profiles/r7_lisi_bench.json`, median of %d): %.0f ms per call, of which the neighbour search %.0f ms and the LISI stage %.1f ms"
+                             "; the GEMM bound is %.0f ms, so the search runs at %.2f of the fp32 matrix-core peak. Kernel trace (one run): %s."
+                             % (lb["repeats"], lb["ms_median"], lb["median_ms_knn"], lb["median_ms_lisi"], lb["bound_ms_gemm_fp32_mfma"],
+                                lb["bound_ms_gemm_fp32_mfma"] / lb["median_ms_knn"], kt or "not collected"))
+else:
+    vals["LISI_MEASURED"] = "**Not measured yet**: `profiles/r7_lisi_bench.json` (written by `tools/lisi_bench.py` on an MI355X) is not in the tree."
 parts = sorted(f for f in os.listdir(os.path.join(ROOT, "docs", "design_parts")) if f.endswith(".md"))
 out = io.StringIO()
 for f in parts:

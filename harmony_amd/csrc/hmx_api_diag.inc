@@ -174,6 +174,13 @@ int64_t hmx_get(hmx_ctx* ctx, const char* field, double* out, int64_t cap) {
   if (f == "carried_rounds") return scalar((double)ctx->carried_rounds);
   if (f == "rounds_without_R") return scalar((double)ctx->rounds_without_R);
   if (f == "chain_rounds") return scalar((double)ctx->chain_rounds);
+  if (f.rfind("launch:", 0) == 0) {      // the last k_tile launch of a kind as it ran: valid, bf, nct, mode, wps, usig, threads, blocks, lds
+    for (int k = 0; k < 5; k++) if (f.substr(7) == TILE_KIND_NAME[k] && ctx->tile_seen[k]) {
+      const TileLaunch& t = ctx->last_tile[k];
+      return vec(std::vector<double>{(double)t.valid, (double)t.bf, (double)t.nct, (double)t.mode, (double)t.wps, (double)t.usig, (double)t.threads, (double)t.blocks, (double)t.lds});
+    }
+    return -1;      // (no such kind, or no launch of it on this handle yet)
+  }
   // further values of the launch plan (hmx_plan.h) as hmx_setup took them, for tests that claim a path
   if (f == "need_lorder") return scalar((double)ctx->D.need_lorder);     // the shuffle also writes lorder / lcombo (k_oldsum's gather variant reads them)
   if (f == "objslots") return scalar((double)ctx->D.objslots);           // slot rows of a round's objective partials: min(n_blocks, 64)

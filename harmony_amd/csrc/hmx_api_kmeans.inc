@@ -72,7 +72,7 @@ int kmeans_centers(hmx_ctx* ctx) {
   // the race on the matrix cores (k_tile mode 3)
   auto seed_probe = [&](const unsigned* excl, int nexcl) -> int {
     ctx->D.seed_key = ctx->seed; ctx->D.seed_goff = (unsigned long long)ctx->goff; ctx->D.seed_excl = excl; ctx->D.seed_nexcl = nexcl;
-    l_tile_static(ctx->L, ctx->D, 3); KCHK();
+    CHK(tile_ran(ctx, TileKind::Seed, l_tile_static(ctx->L, ctx->D, TileKind::Seed))); KCHK();
     return 0;
   };
   CHK(seed_probe(nullptr, 0));
@@ -101,10 +101,10 @@ int kmeans_centers(hmx_ctx* ctx) {
   CHK(gather_centres(ctx, gcells, d_gcells, d_rows));
   // 10 x one Lloyd iteration (:53-64); the centre update runs on the device, no host round trip per iteration
   // (the tile kernel stages the centroid image next to the K x d sum table; where both do not fit, k_lloyd sums into memory)
-  const bool tile_ok = (size_t)D.NQ * D.NS * 1024 + ((size_t)K * d + K) * 8 <= 160 * 1024;
+  const bool tile_ok = lloyd_tile_fits(D.NQ, D.NS, K, d);
   for (int it = 0; it < 10; it++) {
     if (it == 0) HIPCHK(hipMemsetAsync(D.lsum, 0, sizeof(long long) * ((size_t)K * d + K), ctx->L.stream));   // sums + counts: one buffer (k_lloyd_finish leaves it zeroed for the next iteration)
-    if (tile_ok) { l_tile_static(ctx->L, D, 2); KCHK(); }
+    if (tile_ok) { CHK(tile_ran(ctx, TileKind::Lloyd, l_tile_static(ctx->L, D, TileKind::Lloyd))); KCHK(); }
     else { l_lloyd(ctx->L, D); KCHK(); }
     CHK(allreduce(ctx, D.lsum, (int64_t)K * d + K, 0));   // sums and counts in one collective
     l_lloyd_finish(ctx->L, D); KCHK();

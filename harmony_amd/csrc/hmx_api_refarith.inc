@@ -382,7 +382,7 @@ int update_R_ref(hmx_ctx* ctx) {
     float* tot = ctx->sq_total + (size_t)j * W;
     // one launch: the previous block goes back in, this block comes out, this block's penalty table (:329-330, :312-313, :322)
     { PhaseScope ph(ctx, "EO_update"); l_oe_fold(ctx->L, D, ctx->Of, ctx->Ef, put_back, tot, D.pen, 0); KCHK(); }
-    { Launch Le; CHK(launch_with_events(ctx, Le)); l_update(Le, D, j); KCHK(); if (ctx->profile) ctx->prof_update_steps++; }
+    { Launch Le; CHK(launch_with_events(ctx, Le)); CHK(tile_ran(ctx, TileKind::Update, l_update(Le, D, j))); KCHK(); if (ctx->profile) ctx->prof_update_steps++; }
     { PhaseScope ph(ctx, "EO_update");
       // the same cells in the same order as the sums removed above, their R rows updated: that run's segment starts are this run's first guess
       CHK(seq_run_oe(ctx, P, ctx->roundlist, ctx->roundlev, j, 1, true)); }

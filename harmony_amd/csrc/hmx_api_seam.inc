@@ -230,6 +230,7 @@ struct hmx_ctx {
   // that fails half way leaves it false, and the getters / the correction refuse to consume stale rows.  r_store_always: HMX_R_STORE=1, read at setup.
   bool R_valid = false, r_store_always = false;
   int64_t rounds_without_R = 0;
+  TileLaunch last_tile[5]; bool tile_seen[5] = {};      // the last k_tile launch of every TileKind, as it ran (hmx_get "launch:<kind>")
   int64_t carried_rounds = 0;
   bool chain_ok = false; int chain_wgs = 0; uint64_t chain_rounds = 0;   // persistent block chain (one launch per round)
   int tun_tpw = -1, tun_wps = -1;  // tunables set through hmx_set_int before setup
@@ -365,6 +366,12 @@ int allreduce(hmx_ctx* ctx, void* buf, int64_t count, int dtype) {
 }
 #define CHK(expr) do { int s_ = (expr); if (s_) return s_; } while (0)
 #define KCHK() HIPCHK(hipGetLastError())
+// a k_tile launch as its launcher returned it: kept for hmx_get("launch:<kind>"); one that could not be made is a limit of the shape
+int tile_ran(hmx_ctx* ctx, TileKind kind, const TileLaunch& t) {
+  ctx->last_tile[(int)kind] = t; ctx->tile_seen[(int)kind] = true;
+  return t.valid ? 0 : fail(ctx, HMX_ERR_LIMIT, std::string("no k_tile launch for kind ") + TILE_KIND_NAME[(int)kind] + ": NCT " + std::to_string(t.nct) + ", mode " + std::to_string(t.mode) +
+                                                    ", " + std::to_string(t.lds) + " bytes of LDS (" + (t.lds > LDS_PER_CU ? "over a compute unit's" : "no such instantiation") + ")");
+}
 
 // profile mode only: bracket a group of launches with an event pair tagged `name`
 struct PhaseScope {
@@ -508,7 +515,7 @@ int head_pass(hmx_ctx* ctx, bool normalise = false) {   // normalise: Z_corr <- 
   ctx->R_valid = false;
   // O, the contribution replicas, the objective slots (and a stale old-contribution table): ONE launch instead of three or four memsets
   l_zero4(ctx->L, D.O_fx, (size_t)D.B * D.K, D.Snew_fx, (size_t)D.nrep * D.B * D.K, D.objpart, 2 * (size_t)D.objslots * D.nwmax, zero_sold, n_sold); KCHK();
-  l_tile_static(ctx->L, D, 1); KCHK();      // MFMA tiles; O contributions land in the Snew replicas
+  CHK(tile_ran(ctx, TileKind::Head, l_tile_static(ctx->L, D, TileKind::Head))); KCHK();      // MFMA tiles; O contributions land in the Snew replicas
   l_fold(ctx->L, D, -1, 0); KCHK();         // O = sum of the replicas
   l_obj_reduce(ctx->L, D); KCHK();
   CHK(allreduce(ctx, D.O_fx, (int64_t)D.B * D.K, 0));

@@ -236,7 +236,7 @@ static int plan_device(hmx_ctx* ctx, const Design& G, Plan& P) {
   ctx->r_store_always = P.r_store_always; ctx->carry_ok = P.carry_ok; ctx->shuf_inv = P.shuf_inv; ctx->solve_on_device = P.solve_on_device;
   ctx->fused_ok = P.fused_ok; ctx->chain_ok = P.chain_ok; ctx->chain_wgs = P.chain_wgs;
   ctx->oset_mask = 3; ctx->sort_overlap = true;      // four order sets: the batched shuffle (the per-round schedule lost round 4; its switches are gone)
-  ctx->carried_rounds = 0; ctx->chain_rounds = 0; ctx->y_on_device = false; ctx->solve_pending = false;
+  ctx->carried_rounds = 0; ctx->chain_rounds = 0; std::fill(ctx->tile_seen, ctx->tile_seen + 5, false); ctx->y_on_device = false; ctx->solve_pending = false;
   ctx->sold_cur = 0; ctx->sold_state[0] = ctx->sold_state[1] = 1; ctx->sets_clean = false;
   return 0;
 }

@@ -86,7 +86,7 @@ int update_R(hmx_ctx* ctx) {
       const void*& owner = gate.owner[ctx->device];
       if (!ev) HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
       else if (owner != (const void*)ctx->L.stream) HIPCHK(hipStreamWaitEvent(ctx->L.stream, ev, 0));   // (the same stream orders its own launches: no event, ~20 us of barrier packet less per round)
-      { Launch Le; CHK(launch_with_events(ctx, Le)); l_chain(Le, D, ctx->chain_wgs); KCHK(); }
+      { Launch Le; CHK(launch_with_events(ctx, Le)); CHK(tile_ran(ctx, TileKind::Chain, l_chain(Le, D, ctx->chain_wgs))); KCHK(); }
       HIPCHK(hipEventRecord(ev, ctx->L.stream));
       owner = (const void*)ctx->L.stream;
     }
@@ -104,7 +104,7 @@ int update_R(hmx_ctx* ctx) {
     D.fused_fold = 1;
     for (int j = 0; j < D.nb; j++) {
       D.fold_prev = D.Snew_set[(j + 2) % 3]; D.Snew_fx = D.Snew_set[j % 3]; D.fold_zero = D.Snew_set[(j + 1) % 3];
-      { Launch Le; CHK(launch_with_events(ctx, Le)); l_update(Le, D, j); KCHK(); }
+      { Launch Le; CHK(launch_with_events(ctx, Le)); CHK(tile_ran(ctx, TileKind::Update, l_update(Le, D, j))); KCHK(); }
       if (ctx->profile) ctx->prof_update_steps++;
       if (sharded) CHK(allreduce(ctx, D.Snew_fx, (int64_t)D.nrep * D.B * D.K, 0));   // this block's new contribution, all ranks
       std::swap(D.O_fx, D.O_alt);   // workgroup 0 published O' into O_alt
@@ -131,7 +131,7 @@ int update_R(hmx_ctx* ctx) {
       if (j < D.nb) { l_penalty(ctx->L, D); KCHK(); }
     }
     if (j == D.nb) break;
-    { Launch Le; CHK(launch_with_events(ctx, Le)); l_update(Le, D, j); KCHK(); if (ctx->profile) ctx->prof_update_steps++; }
+    { Launch Le; CHK(launch_with_events(ctx, Le)); CHK(tile_ran(ctx, TileKind::Update, l_update(Le, D, j))); KCHK(); if (ctx->profile) ctx->prof_update_steps++; }
   }
   if (chain_tail) {
     ctx->sold_state[ctx->sold_cur] = 0;

@@ -206,7 +206,6 @@ void l_normalize(const Launch& L, float* Z, int n, int d, int zs);
 void l_normalize_from(const Launch& L, const float* src, float* dst, int n, int d, int zs);
 // objective partials of the current state (reads R)
 void l_head(const Launch& L, const Dev& D);
-void l_tile_static(const Launch& L, const Dev& D, int mode);
 void l_sort_blocks(const Launch& L, const Dev& D, bool fused, uint64_t seed, uint64_t round, uint64_t Nglob, uint64_t goff,
                    uint64_t cells_per_block);
 void l_sort_hist(const Launch& L, const Dev& D, bool fused, uint64_t seed, uint64_t round, uint64_t Nglob, uint64_t goff, uint64_t cells_per_block);
@@ -226,12 +225,14 @@ void l_penalty(const Launch& L, const Dev& D);
 void l_foldpen(const Launch& L, const Dev& D, int j, const long long* Oin, long long* Oout, const long long* Sin,
                long long* Szero);
 void l_obj_reduce(const Launch& L, const Dev& D);
-void l_update(const Launch& L, const Dev& D, int j);
-void l_chain(const Launch& L, const Dev& D, int workgroups);
-// the same three launchers of the translation unit built with HMX_TILE_BF=1 (hmx_tile_bf.hip): k_tile with the split-bf16 distance GEMM
-void l_tile_static_bf(const Launch& L, const Dev& D, int mode);
-void l_update_bf(const Launch& L, const Dev& D, int j);
-void l_chain_bf(const Launch& L, const Dev& D, int workgroups);
+// the k_tile launches (head / Lloyd / seeding race, block update of block j, a round's chain), planned by plan_tile_launch (hmx_plan.h); returned: the launch as it ran -- valid = false: none, the caller reports HMX_ERR_LIMIT
+struct TileLaunch; enum class TileKind;
+TileLaunch l_tile_static(const Launch& L, const Dev& D, TileKind kind);
+TileLaunch l_update(const Launch& L, const Dev& D, int j);
+TileLaunch l_chain(const Launch& L, const Dev& D, int workgroups);
+// a planned launch on the k_tile of the fp32 build (hmx_kernels.hip) / of the split-bf16 build (hmx_tile_bf.hip, HMX_TILE_BF=1); false: no such instantiation
+bool dispatch_k_tile(const Launch& L, const Dev& D, const TileLaunch& t, int j);
+bool dispatch_k_tile_bf(const Launch& L, const Dev& D, const TileLaunch& t, int j);
 void l_round_tail(const Launch& L, const Dev& D, double* host_slot, long long* z0, size_t n0, long long* z1, size_t n1);
 // Cluster <-> MFMA column mapping of the tile kernels.  Lane (g, c) of a wave holds column c of every 16-wide cluster tile ct.
 // Clusters are dealt so that a lane's columns are CONSECUTIVE clusters: within a full quad of cluster tiles (4q..4q+3) the lane
@@ -305,7 +306,6 @@ void l_gather_rows(const Launch& L, const Dev& D, const long long* gcells, uint6
 void l_lloyd(const Launch& L, const Dev& D);
 void l_lloyd_finish(const Launch& L, const Dev& D);
 void l_y_images(const Launch& L, const Dev& D, const double* rows, int normalise);
-size_t lds_bytes_y(const Dev& D);
 
 // ---- query mapping and reference summary (hmx_query.hip) -----------------------------------------------------------------------------
 struct QueryDev {

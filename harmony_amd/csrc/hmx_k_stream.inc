@@ -444,6 +444,19 @@ __global__ __launch_bounds__(1024) void k_shuf_place(Dev D, ShufBatch S) {
       for (int k = c; k < pad; k++) { if (D.need_lorder) lo_[st + k] = -1; lp[st + k] = make_int2(-1, -1); }
     }
 }
+// oe_arith: the round's shuffled order itself, posord[position] = internal cell id (arma::shuffle's update_order, src/harmony.cpp:272-273,
+// for the documented generator: cell g sits at position feistel(seed, round, g))
+__global__ void k_ref_posord(Dev D, FeistelKeys fk, uint64_t Nglob, int* __restrict__ posord, int* __restrict__ poslev) {
+  for (int g = blockIdx.x * blockDim.x + threadIdx.x; g < D.n; g += gridDim.x * blockDim.x) {
+    const int cell = D.invperm[g];
+    const size_t pos = (size_t)feistel_apply(fk, Nglob, (uint64_t)g);
+    posord[pos] = cell;
+    if (poslev) {       // the position's level codes, [c][n]: the sequential-sum kernels then need no combo / qlev lookups
+      const int q = D.combo[cell];
+      for (int c = 0; c < D.C && c < 4; c++) poslev[(size_t)c * D.n + pos] = D.qlev[q * D.C + c];
+    }
+  }
+}
 
 // --------------------------------------------------------------------------------------
 // update_R (src/harmony.cpp:269-342): the streaming passes around the block update (k_tile MODE 0, hmx_k_tile.inc)
@@ -653,6 +666,112 @@ __global__ void k_obj_final(Dev D) {
   double a = 0.0, b = 0.0;
   for (int s = 0; s < D.objslots; s++) { a += D.objrow[2 * s]; b += D.objrow[2 * s + 1]; }
   D.obj[0] = a; D.obj[1] = b;
+}
+// One GPU: the three kernels that close a clustering round (slot rows -> obj[0..1] -> cross-entropy term, snapshot, chain control
+// reset) as ONE launch: every workgroup reduces its slot row, the last one to finish (ticket) does the rest.  Same fixed-order sums.
+__global__ __launch_bounds__(1024) void k_round_tail(Dev D, double* __restrict__ host_slot, long long* __restrict__ z0, size_t n0,
+                                                      long long* __restrict__ z1, size_t n1) {
+  __shared__ double ra[1024], rb[1024];
+  __shared__ int last;
+  const int tid = threadIdx.x;
+  {  // the old-contribution table this round consumed and the replica sets start the next rounds from zero: cleared here instead
+     // of by memset launches
+    for (size_t i = (size_t)blockIdx.x * 1024 + tid; i < n0; i += (size_t)gridDim.x * 1024) z0[i] = 0;
+    for (size_t i = (size_t)blockIdx.x * 1024 + tid; i < n1; i += (size_t)gridDim.x * 1024) z1[i] = 0;
+  }
+  double a = 0.0, b = 0.0;
+  double* row = D.objpart + (size_t)blockIdx.x * D.nwmax * 2;
+  for (int i = tid; i < D.nwmax; i += 1024) { a += row[2 * i]; b += row[2 * i + 1]; row[2 * i] = 0.0; row[2 * i + 1] = 0.0; }
+  ra[tid] = a; rb[tid] = b;
+  __syncthreads();
+  for (int off = 512; off > 0; off >>= 1) {
+    if (tid < off) { ra[tid] += ra[tid + off]; rb[tid] += rb[tid + off]; }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    // No fences: an agent-scope release here would write back everything the round left dirty in this XCD's L2 (tens of MB of R
+    // rows).  The two sums go out as write-through device-scope stores, the ticket follows once they are acknowledged, and the
+    // last workgroup reads them with device-scope loads (the scheme of the block chain, DESIGN 4.1).
+    __hip_atomic_store(&D.objrow[2 * blockIdx.x], ra[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(&D.objrow[2 * blockIdx.x + 1], rb[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    last = (atomicAdd(D.tail_ticket, 1) == (int)gridDim.x - 1) ? 1 : 0;
+  }
+  __syncthreads();
+  if (!last) return;
+  const int K = D.K, B = D.B;
+  double cross = 0.0;
+  // many levels (B >= 64; configs[4]: 200 x 200 entries, each a division and a logarithm): G threads per cluster take every G-th level and their partial sums are
+  // added in ascending order -- one thread per cluster needed 75 of this launch's 88 us (rocprofv3, round 6), 2.1 ms of a 52 ms run.  (The level sums then
+  // associate differently from k_objective_tables': ~1e-16 of the term.)
+  const int G = (B >= 64 && K <= 512) ? min(8, 1024 / K) : 1;
+  if (G > 1) {
+    const int k = tid % K, j = tid / K;
+    double part = 0.0;
+    if (j < G) {
+      long long rs = 0;
+      for (int b0 = 0; b0 < D.B0; b0++) rs += D.O_fx[(size_t)b0 * K + k];
+      const double rsd = (double)rs * FX_INV;
+      for (int bb = j; bb < B; bb += G) {
+        const double od = (double)D.O_fx[(size_t)bb * K + k] * FX_INV;
+        const float o = (float)od, e = (float)(rsd * (double)D.Pr_b[bb]);
+        const float m = D.theta[bb] * logf((o + e + 1.0f) / ((2.0f * e) + 1.0f));
+        part += od * (double)m;
+      }
+    }
+    __syncthreads();
+    rb[tid] = part;
+    __syncthreads();
+    if (tid < K) {
+      double ck = 0.0;
+      for (int jj = 0; jj < G; jj++) ck += rb[jj * K + tid];
+      cross = ck * (double)D.sigma[tid];
+    }
+  } else
+  for (int k = tid; k < K; k += 1024) {      // (same arithmetic as k_objective_tables)
+    long long rs = 0;
+    for (int b0 = 0; b0 < D.B0; b0++) rs += D.O_fx[(size_t)b0 * K + k];
+    const double rsd = (double)rs * FX_INV;
+    double ck = 0.0;
+    for (int bb = 0; bb < B; bb++) {
+      const double od = (double)D.O_fx[(size_t)bb * K + k] * FX_INV;
+      const float o = (float)od, e = (float)(rsd * (double)D.Pr_b[bb]);
+      const float m = D.theta[bb] * logf((o + e + 1.0f) / ((2.0f * e) + 1.0f));
+      ck += od * (double)m;
+    }
+    cross += ck * (double)D.sigma[k];
+  }
+  __syncthreads();
+  ra[tid] = cross;
+  __syncthreads();
+  // (K <= 256: every thread holds at most one cluster, the entries from 256 on are zero -- the same pairwise tree as
+  //  k_objective_tables' 256-entry one, preceded by two levels that add zeros: identical bits)
+  for (int off = 512; off > 0; off >>= 1) {
+    if (tid < off) ra[tid] += ra[tid + off];
+    __syncthreads();
+  }
+  // the slot rows' sums: fetched by 2 x objslots threads at once (objslots <= 64), added in slot order by one -- the 40 device-scope
+  // loads used to be ONE thread's dependent chain, ~20 us of every round
+  if (tid < 2 * D.objslots) rb[tid] = __hip_atomic_load(&D.objrow[tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __syncthreads();
+  if (tid == 0) {
+    double sa = 0.0, sb = 0.0;
+    for (int sl = 0; sl < D.objslots; sl++) { sa += rb[2 * sl]; sb += rb[2 * sl + 1]; }
+    D.obj[0] = sa; D.obj[1] = sb;
+    D.obj[2] = sa; D.obj[3] = sb; D.obj[4] = ra[0];
+    // error word of the snapshot: the chain's code (< 16) + 16 if a ridge system of the correction before this round was singular
+    const double err = (D.chain_ctl ? (double)D.chain_ctl[1] : 0.0) + ((D.solve_err && *D.solve_err) ? 16.0 : 0.0);
+    D.obj[5] = err;
+    if (host_slot) {     // pinned host memory, mapped into the device: visible to the host once the event behind this launch completed
+      __hip_atomic_store(&host_slot[0], sa, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      __hip_atomic_store(&host_slot[1], sb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      __hip_atomic_store(&host_slot[2], ra[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      __hip_atomic_store(&host_slot[3], err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+    *D.tail_ticket = 0;
+  }
+  __syncthreads();
+  if (D.chain_ctl) for (int i = tid; i < 8 * D.nb + 24; i += 1024) D.chain_ctl[i] = 0;
 }
 // Single-launch variant (one GPU): fold + penalty with ping-pong tables, so no thread reads what another writes;
 // one workgroup per 16 clusters, the new O column block goes through LDS for the covariate-0 row sums.

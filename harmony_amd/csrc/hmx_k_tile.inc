@@ -426,9 +426,6 @@ __device__ __forceinline__ void flush_tile_fx(long long* __restrict__ tab, long 
 // below this index are always completely inside K, only the ones from it on can hold k >= K.
 // (cluster tiles are grouped in quads by kcol: the tiles of the last group can hold k >= K)
 constexpr int first_partial_ct(int nct) { return (nct & 3) ? 4 * (nct >> 2) : 4 * ((nct >> 2) - 1); }
-// Static-tile launches (head / Lloyd / seeding) use 256-thread workgroups, capped at one resident generation
-// (D.static_maxblocks); measured: 768-thread workgroups (one per CU) are 30% slower (tail effect).
-constexpr int tile_threads(int nct) { return 256; }
 // MODE 0: block update (cells gathered through lpair, penalty in the exponent, ONE normalisation)  update_R :318-330
 // MODE 1: head (static 16-cell tiles of the internal order, plain softmax)                 :141-150 / :221-227
 // Register budget: K > 64 runs 2 waves per SIMD (<= 256 VGPRs: row prefetch + two accumulator sets, K <= 112);

@@ -11,11 +11,12 @@
 // R sums (exact, order-independent => bit-reproducible and shard-count independent),
 // fp64 for the rest.
 #include "hmx_internal.h"
+#include "hmx_plan.h"
 #include <float.h>
 #include <hip/hip_ext.h>
 
 #ifndef HMX_TILE_BF
-#define HMX_TILE_BF 0         // 1 (hmx_tile_bf.hip): this translation unit builds ONLY k_tile, with the split-bf16 distance GEMM, and its three launchers
+#define HMX_TILE_BF 0         // 1 (hmx_tile_bf.hip): this translation unit builds ONLY k_tile, with the split-bf16 distance GEMM, and its dispatch
 #endif
 
 namespace hmx {
@@ -83,6 +84,171 @@ __device__ __forceinline__ float pen_pow(float num, float den, float theta) {
   const float x = num * __builtin_amdgcn_rcpf(den);
   return __builtin_amdgcn_exp2f(theta * __builtin_amdgcn_logf(x));
 }
+#if !HMX_TILE_BF      // ---- peer inboxes beyond the chain's own exchanges: connection self-test and the small / large all-reduces ----
+// Self-test of the peer-to-peer inboxes, run by every rank at the same time before the chain may use them: P2P_TEST_STEPS exchanges of
+// a 2048-entry table with known contents through exactly the chain's code path (p2p_send, the same slots, parities and polls),
+// every received value checked.  result[0] = wrong or missing values (0 = pass), result[1] = 100 MHz ticks of the steps after the
+// first (the first absorbs the launch skew between the ranks; bounded at ~3 s).
+constexpr int P2P_TEST_STEPS = 64;
+__device__ __forceinline__ long long p2p_test_value(int rank, int step, int i) {
+  const long long v = (long long)(rank + 1) * 0x100000001ll * (long long)(i + 1) + (long long)step * 7919;
+  return ((i + step) & 1) ? -v : v;
+}
+__global__ void __launch_bounds__(512) k_p2p_selftest(Dev D, unsigned tag, int* result) {
+  const int tid = threadIdx.x, G = D.p2p_world, me = D.p2p_rank;
+  __shared__ int gave_up, bad;
+  if (tid == 0) { gave_up = 0; bad = 0; }
+  __syncthreads();
+  int wrong = 0;
+  unsigned long long t1 = 0;
+  for (int step = 0; step < P2P_TEST_STEPS; step++) {
+    if (step == 1) t1 = wall_clock64();
+    const unsigned tagx = tag + (unsigned)step;
+    const size_t par = (size_t)(step & 1) * 8;      // (the chain's two planes)
+#pragma unroll
+    for (int e = 0; e < 4; e++) p2p_send(D, par, tid + e * 512, tagx, p2p_test_value(me, step, tid + e * 512));
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+      const int i = tid + e * 512;
+#pragma unroll
+      for (int gq = 0; gq < 8; gq++) if (gq < G && gq != me) {
+        const unsigned long long* src = D.p2p_inbox_self() + ((par + gq) * P2P_CAP + i) * 2;
+        unsigned long long lo = 0, hi = 0;
+        bool got = false;
+        for (int spins = 0; spins < (1 << 20); spins++) {
+          lo = __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+          hi = __hip_atomic_load(src + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+          if ((unsigned)(lo >> 32) == tagx && (unsigned)(hi >> 32) == tagx) { got = true; break; }
+          if ((spins & 63) == 63 && __hip_atomic_load(&gave_up, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) break;
+          if (step == 0) __builtin_amdgcn_s_sleep(100); else __builtin_amdgcn_s_sleep(2);
+        }
+        if (!got) { __hip_atomic_store(&gave_up, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); wrong++; }
+        else if ((long long)((hi << 32) | (lo & 0xffffffffull)) != p2p_test_value(gq, step, i)) wrong++;
+      }
+    }
+  }
+  const unsigned long long t2 = wall_clock64();
+  if (wrong) atomicAdd(&bad, wrong);
+  __syncthreads();
+  if (tid == 0) { result[0] = bad; result[1] = (int)(t2 - t1); }
+}
+// Generic all-reduce of a small buffer through the peers' inboxes (planes 2 / 3): the collectives of a run that are NOT block steps --
+// O after a head, the objective's two sums, the Lloyd sums and counts, the seeding minima, small ridge statistics -- are a few KB each
+// and latency-bound: as host-launched ncclAllReduce calls they cost a launch + a ring each (~50 per run).  Here: one workgroup, every
+// rank writes its values straight into every peer's inbox (self-validating {tag, half} granules, as the chain does) and adds up what
+// arrived in its own, in RANK ORDER (fp64 sums are then identical on every rank).  A rank can be at most one call ahead of a peer (it
+// needs the peer's values of call n to finish call n), so two planes alternate.  Every spin is bounded; a timeout raises *err (the
+// chain's error word: it reaches the host with the next objective snapshot).
+__global__ void __launch_bounds__(1024) k_p2p_allreduce(Dev D, unsigned long long* __restrict__ buf, int n, int dtype, unsigned seq, int* err) {
+  const int tid = threadIdx.x, G = D.p2p_world, me = D.p2p_rank;
+  const unsigned tag = 0x40000000u + (seq & 0x3fffffffu);
+  const size_t par = (size_t)(2 + (seq & 1u)) * 8;
+  for (int base = 0; base < n; base += 1024 * 4) {
+    unsigned long long mine[4];
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+      const int i = base + tid + e * 1024;
+      mine[e] = (i < n) ? buf[i] : 0ull;
+      if (i < n) p2p_send(D, par, i, tag, (long long)mine[e]);
+    }
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+      const int i = base + tid + e * 1024;
+      if (i >= n) continue;
+      unsigned long long val[8];
+#pragma unroll
+      for (int gq = 0; gq < 8; gq++) {
+        val[gq] = mine[e];
+        if (gq < G && gq != me) {
+          const unsigned long long* src = D.p2p_inbox_self() + ((par + gq) * P2P_CAP + i) * 2;
+          unsigned long long lo = 0, hi = 0;
+          bool got = false;
+          for (int spins = 0; spins < (1 << 20); spins++) {
+            lo = __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            hi = __hip_atomic_load(src + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            if ((unsigned)(lo >> 32) == tag && (unsigned)(hi >> 32) == tag) { got = true; break; }
+            if ((spins & 255) == 255 && err && __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) break;
+            __builtin_amdgcn_s_sleep(2);
+          }
+          if (!got && err) atomicExch(err, 7);
+          val[gq] = (hi << 32) | (lo & 0xffffffffull);
+        }
+      }
+      unsigned long long out;
+      if (dtype == 1) { double a = 0.0; for (int gq = 0; gq < G; gq++) a += __longlong_as_double((long long)val[gq]); out = (unsigned long long)__double_as_longlong(a); }
+      else if (dtype == 2) { long long a = (long long)val[0]; for (int gq = 1; gq < G; gq++) a = min(a, (long long)val[gq]); out = (unsigned long long)a; }
+      else { long long a = 0; for (int gq = 0; gq < G; gq++) a += (long long)val[gq]; out = (unsigned long long)a; }
+      buf[i] = out;
+    }
+  }
+}
+// LARGE buffers (the ridge statistics of many-level designs: Q K (d + 1) doubles, 10 MB at BASELINE configs[4]) through the same inboxes as
+// reduce-scatter + all-gather: the one-shot form above would push every rank's WHOLE buffer over each of its links; here entry e of a
+// window belongs to rank e / S (S = P2P_CAP / 2 entries per rank and window): (1) every rank sends its value of e to the owner only, (2) the owner
+// adds the G values in RANK ORDER (fp64 sums identical on every rank) and sends the result to everybody, (3) the others pick it up -- 2 (G - 1) / G
+// of the buffer per link instead of (G - 1) times it, many workgroups wide.  Inbox layout per (plane, source): entries [0, S) carry the
+// scattered values, [S, 2 S) the gathered results; planes and tags as k_p2p_allreduce (one call = one window = one `seq`).  Three separate
+// sweeps, so no thread waits while a peer still needs one of its sends; every spin is bounded (err = 7).
+__device__ __forceinline__ void p2p_send_to(const Dev& D, int peer, size_t par, int i, unsigned tag, unsigned long long v) {
+  const unsigned long long tb = (unsigned long long)tag << 32;
+  const unsigned long long lo = tb | (v & 0xffffffffull), hi = tb | (v >> 32);
+#pragma unroll
+  for (int gq = 0; gq < 8; gq++) if (gq == peer) {       // (static indices only: a dynamic one would spill the kernarg copy)
+    unsigned long long* dst = D.p2p_inbox[gq] + ((par + D.p2p_rank) * P2P_CAP + i) * 2;
+    __hip_atomic_store(dst, lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(dst + 1, hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+}
+__device__ __forceinline__ unsigned long long p2p_wait(const Dev& D, size_t par, int src_rank, int i, unsigned tag, int* err) {
+  const unsigned long long* src = D.p2p_inbox_self() + ((par + src_rank) * P2P_CAP + i) * 2;
+  unsigned long long lo = 0, hi = 0;
+  bool got = false;
+  // bounded by the wall clock, not by a spin count: the windows of a large buffer follow rank-local phases of very different length (ridge
+  // statistics of a 10M-cell shard), so a peer may legitimately arrive seconds late; wall_clock64 ticks at 100 MHz: 3 s, as the self-test
+  const unsigned long long t_in = wall_clock64();
+  for (int spins = 0;; spins++) {
+    lo = __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    hi = __hip_atomic_load(src + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    if ((unsigned)(lo >> 32) == tag && (unsigned)(hi >> 32) == tag) { got = true; break; }
+    if ((spins & 255) == 255) {
+      if (err && __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) break;
+      if (wall_clock64() - t_in > 300000000ull) break;
+    }
+    __builtin_amdgcn_s_sleep(2);
+  }
+  if (!got && err) atomicExch(err, 7);
+  return (hi << 32) | (lo & 0xffffffffull);
+}
+__global__ void __launch_bounds__(1024) k_p2p_allreduce_big(Dev D, unsigned long long* __restrict__ buf, int n, int dtype, unsigned seq, int* err) {
+  const int G = D.p2p_world, me = D.p2p_rank;
+  constexpr int S = P2P_CAP / 2;
+  const unsigned tag = 0x40000000u + (seq & 0x3fffffffu);
+  const size_t par = (size_t)(2 + (seq & 1u)) * 8;
+  const int t0 = blockIdx.x * blockDim.x + threadIdx.x, nt = gridDim.x * blockDim.x;
+  for (int e = t0; e < n; e += nt) {                       // (1) scatter: my value of every entry another rank owns
+    const int owner = e / S;
+    if (owner != me) p2p_send_to(D, owner, par, e - owner * S, tag, buf[e]);
+  }
+  for (int l = t0; l < S; l += nt) {                       // (2) my slice: reduce in rank order, gather out
+    const int e = me * S + l;
+    if (e >= n) break;
+    unsigned long long val[8];
+#pragma unroll
+    for (int gq = 0; gq < 8; gq++) { val[gq] = buf[e]; if (gq < G && gq != me) val[gq] = p2p_wait(D, par, gq, l, tag, err); }
+    unsigned long long out;
+    if (dtype == 1) { double a = 0.0; for (int gq = 0; gq < G; gq++) a += __longlong_as_double((long long)val[gq]); out = (unsigned long long)__double_as_longlong(a); }
+    else if (dtype == 2) { long long a = (long long)val[0]; for (int gq = 1; gq < G; gq++) a = min(a, (long long)val[gq]); out = (unsigned long long)a; }
+    else { long long a = 0; for (int gq = 0; gq < G; gq++) a += (long long)val[gq]; out = (unsigned long long)a; }
+    buf[e] = out;
+#pragma unroll
+    for (int gq = 0; gq < 8; gq++) if (gq < G && gq != me) p2p_send_to(D, gq, par, S + l, tag, out);
+  }
+  for (int e = t0; e < n; e += nt) {                       // (3) the other ranks' slices
+    const int owner = e / S;
+    if (owner != me) buf[e] = p2p_wait(D, par, owner, S + (e - owner * S), tag, err);
+  }
+}
+#endif  // !HMX_TILE_BF
 
 // counter-based generators -- same SPEC as include/harmony_mi355x.h documents
 __host__ __device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
@@ -190,10 +356,10 @@ __device__ __forceinline__ void flush_fx(long long* __restrict__ tab, const int*
 // --------------------------------------------------------------------------------------
 // ingest / egress
 // The kernels live in four include files (one translation unit: they share the helpers above and each other's device functions):
-//   hmx_k_stream.inc   ingest / egress, shuffle and sort, old-contribution passes, fold / penalty, first-generation kernels
+//   hmx_k_stream.inc   ingest / egress, shuffle and sort, old-contribution passes, fold / penalty, round tail, first-generation kernels
 //   hmx_k_tile.inc     the MFMA tile machinery and k_tile (block update, head, Lloyd, seeding, persistent chain) -- also built by hmx_tile_bf.hip
 //   hmx_k_correct.inc  objective tables / terms, MoE ridge correction (statistics, solve, apply), VALU fallbacks
-//   hmx_k_launch.inc   launchers, peer-inbox self-test and all-reduces -- also built by hmx_tile_bf.hip
+//   hmx_k_launch.inc   launchers (no kernels; a k_tile launch is planned in hmx_plan.h) -- its dispatch_k_tile also built by hmx_tile_bf.hip (the peer-inbox kernels sit beside p2p_send above)
 #include "hmx_k_stream.inc"
 #include "hmx_k_tile.inc"
 #include "hmx_k_correct.inc"

@@ -94,7 +94,9 @@ constexpr double PAIR_MAX_TILES_PER_PAIR = 12.0;
 //  (8.2 %): 165.9 -> 140.5 ms per run (no pass over R for the old contributions: 21.8 ms, no R stores in 21 of 28 rounds); 2.5M cells (16 %): 95.3 / 94.0 ms,
 //  break-even.)
 constexpr int64_t CARRY_PAD_PER_KEY = 8, CARRY_CELLS_PER_PAD = 8;
-constexpr size_t FOLD_LDS_BYTES = 150 * 1024;       // LDS a tile kernel with the fold in its prologue (fused fold, both chains) may take
+constexpr size_t LDS_PER_CU = 160 * 1024;           // LDS of a compute unit: what the workgroups resident on it share
+constexpr size_t LDS_BUDGET = 150 * 1024;           // what the workgroup(s) owning a CU ask for at most: its LDS less room for the kernels' static objects
+constexpr size_t FOLD_LDS_BYTES = LDS_BUDGET, FOLD_LDS_SLACK = 64;       // LDS a tile kernel with the fold in its prologue (fused fold, both chains) may take, less its static words
 constexpr size_t SOLVE_LDS_BYTES = 158 * 1024;      // LDS panel of the device Cholesky
 constexpr int64_t INT32_CELLS = 2147483000ll;       // positions of a padded block order are int32
 // the launch-per-step path gives a wave a contiguous range of a block's tiles once it has several tiles per block
@@ -120,10 +122,24 @@ struct Plan {
 };
 
 inline double tiles_per_wave(const Shape& s) { return (double)s.N / std::max(s.nb, 1) / 16.0 / (8.0 * std::max(s.cus - 1, 1)); }
-// centroid image + O / Snew / penalty tables + combination levels of a tile kernel that folds in its prologue
-inline bool fold_lds_fits(const Plan& p, const Shape& s) {
-  return (size_t)p.NQ * p.NS * 1024 + (size_t)s.B * s.K * 12 + (size_t)s.Q * s.C * 4 + 64 <= FOLD_LDS_BYTES;
+// ---- the LDS of a k_tile launch, term by term (every budget below and plan_tile_launch are sums of these) ---------------------------------
+// centroid image of the fp32 build, [NQ][NS][64 lanes] float4, and of the split-bf16 build, [nct][NS2][3 parts][64 lanes][8 bf16]
+inline size_t image_bytes_f32(int NQ, int NS) { return (size_t)NQ * NS * 1024; }
+inline size_t image_bytes_bf(int nct, int NS2) { return (size_t)nct * NS2 * 3 * 1024; }
+// fold tables behind the image: O' [B][K] int64 (`fold`: the launch folds in its prologue), the penalty table [B][K] fp32 and the combinations' levels [Q][C] (`pen`, or with
+// the fold).  pad4: the launches round the penalty table up to four entries; the budget of fold_lds_fits was written without that rounding and keeps its value (<= 12 bytes apart).
+inline size_t fold_table_bytes(int B, int K, int Q, int C, bool fold, bool pen, bool pad4) {
+  const size_t bk = (size_t)(pad4 ? (B * K + 3) & ~3 : B * K);
+  return (fold ? (size_t)B * K * 8 : 0) + ((pen || fold) ? (bk + (size_t)Q * C) * 4 : 0);
 }
+inline size_t lloyd_sum_bytes(int K, int d) { return ((size_t)K * d + K) * sizeof(long long); }      // Lloyd: int64 sums [K][d] and counts [K]
+// wave-pair chain (MODE 6): workers [ both halves' images | qlev | exchange slots | [8 waves][4 tiles][16 nctp] log2 penalties ], folders [ O slice | cluster masses | this rank's deltas (sharded) ]
+inline size_t pair_worker_bytes(int nctp, int NS2, int Q, int C) { return 2 * image_bytes_bf(nctp, NS2) + (size_t)((Q * C + 3) & ~3) * 4 + 4 * 2 * 2 * 16 * 8 + (size_t)8 * 4 * 16 * nctp * 4; }
+inline size_t pair_folder_bytes(int B, int kw) { return ((size_t)2 * B * kw + kw) * 8; }
+// centroid image + O / Snew / penalty tables + combination levels of a tile kernel that folds in its prologue
+inline bool fold_lds_fits(const Plan& p, const Shape& s) { return image_bytes_f32(p.NQ, p.NS) + fold_table_bytes(s.B, s.K, s.Q, s.C, true, true, false) + FOLD_LDS_SLACK <= FOLD_LDS_BYTES; }
+// Lloyd on the tile kernel: the fp32 image and the sum table fit a CU's LDS (else k_lloyd sums into memory)
+inline bool lloyd_tile_fits(int NQ, int NS, int K, int d) { return image_bytes_f32(NQ, NS) + lloyd_sum_bytes(K, d) <= LDS_PER_CU; }
 
 // Stage 1: everything up to this rank's view of fused_ok / chain_ok.  (Sharded runs then agree on the minimum of both flags.)
 inline Plan plan_shape(const Switches& sw, const Shape& s) {
@@ -197,12 +213,11 @@ inline void plan_pair(const Switches& sw, const Shape& s, Plan& p) {
   if (sw.chain_folders_set) { const int want = std::max(1, sw.chain_folders); kw = ((K + want - 1) / want + 3) & ~3; }
   const int F = (K + kw - 1) / kw;
   const double tiles_per_stream = (double)s.N / std::max(s.nb, 1) / 16.0 / (4.0 * std::max(p.chain_wgs - F, 1));
-  const size_t lds_w = (size_t)2 * nctp * p.NS2 * 3 * 1024 + (size_t)((s.Q * s.C + 3) & ~3) * 4 + 4 * 2 * 2 * 16 * 8 + (size_t)8 * 4 * 16 * nctp * 4;      // + [8 waves][4 tiles][16 nctp] log2 penalties
-  const size_t lds_f = ((size_t)2 * s.B * kw + kw) * 8;      // folders: [ O slice | cluster masses | this rank's deltas (sharded) ]
+  const size_t lds_w = pair_worker_bytes(nctp, p.NS2, s.Q, s.C), lds_f = pair_folder_bytes(s.B, kw);
   const bool want = sw.chain != 0 && sw.chain_pair != 0 &&
                     (sw.chain_pair == 1 || sw.chain == 1 || tiles_per_stream <= (sw.chain_max_tpw_set ? sw.chain_max_tpw : PAIR_MAX_TILES_PER_PAIR));
   p.chain_pair = (want && !p.chain_ok && p.NCT > 7 && nctp >= 4 && nctp <= 7 && K % 4 == 0 && K - KH <= 16 * nctp && K - KH >= 4 && p.usig && p.dot_bf && p.NS2 <= 2 &&
-                  p.NT4 <= 4 && s.nb <= 64 && s.cus >= 64 && F < p.chain_wgs / 4 && !s.oe_arith && !s.obj_arith && std::max(lds_w, lds_f) + 64 <= FOLD_LDS_BYTES) ? 1 : 0;
+                  p.NT4 <= 4 && s.nb <= 64 && s.cus >= 64 && F < p.chain_wgs / 4 && !s.oe_arith && !s.obj_arith && std::max(lds_w, lds_f) + FOLD_LDS_SLACK <= FOLD_LDS_BYTES) ? 1 : 0;
   p.KH = KH; p.chain_folders = F; p.chain_kw = kw;
 }
 
@@ -223,6 +238,75 @@ inline Plan plan_unsharded(const Switches& sw, const Shape& s) {
   Plan p = plan_shape(sw, s);
   if (!p.limit) { plan_pair(sw, s, p); plan_finish(sw, s, p); }
   return p;
+}
+
+// ---- one k_tile launch: which instantiation, of which build, on what grid, with how much LDS -- a pure function of the scalar fields of Dev the tile launchers decide on (hmx_k_launch.inc: tile_geom)
+struct TileGeom {
+  int n = 0, nb = 1, K = 0, d = 0, B = 0, C = 0, Q = 0, NCT = 0, NQ = 0, NS = 0, NS2 = 0, KH = 0, ntitems = 0, nwmax = 0;
+  int upd_tpw = 1, upd_threads = 512, upd_maxblocks = 256, upd_wps = 2, static_maxblocks = 0, usig = 0, dot_bf = 0;
+  bool img3 = false;                           // the split-bf16 image exists (Dev::Yimg3)
+  int fused_fold = 0, pen_lds = 0, chain_pair = 0, chain_kw = 0, r_store = 1;      // (fused_fold, r_store: set per launch by the callers)
+};
+enum class TileKind { Update = 0, Head = 1, Lloyd = 2, Seed = 3, Chain = 4 };      // (= k_tile's MODE of the plain variant)
+constexpr const char* TILE_KIND_NAME[5] = {"update", "head", "lloyd", "seed", "chain"};
+// k_tile<nct, mode, wps, usig> of the split-bf16 (bf) or the fp32 build, `blocks` workgroups of `threads`, `lds` bytes.  mode: the MODE that runs, 5 = chain without R stores,
+// 6 = wave-pair chain (nct: cluster tiles of a half).  valid = false: nothing may be launched (LDS over the CU's, or -- set by the launcher -- no such instantiation).
+struct TileLaunch { bool valid = false, bf = false; int nct = 0, mode = 0, wps = 2; bool usig = false; int threads = 0, blocks = 0; size_t lds = 0; };
+// the split-bf16 build of a launch is taken when the workgroups that are to share a CU still fit its LDS with the larger image
+inline bool bf_fits(const TileGeom& g, size_t rest, long long blocks) {
+  const long long per_cu = (blocks + 255) / 256;
+  return g.dot_bf && g.img3 && (image_bytes_bf(g.NCT, g.NS2) + rest) * (size_t)(per_cu < 1 ? 1 : per_cu) <= LDS_PER_CU;
+}
+inline TileLaunch plan_tile_launch(const TileGeom& g, TileKind kind, int workgroups) {
+  TileLaunch t; t.nct = g.NCT; t.mode = (int)kind;
+  long long blocks = workgroups; size_t rest = 0;
+  if (kind == TileKind::Chain) {      // two waves per SIMD, two accumulator sets; one workgroup per CU (the caller's count)
+    t.threads = 512; t.usig = g.usig != 0;
+    rest = fold_table_bytes(g.B, g.K, g.Q, g.C, true, true, true);
+    if (g.chain_pair) {      // (the wave-pair chain exists in the split-bf16 build only; cluster tiles of a half: K = 116 .. 128 -> 4, .. 160 -> 5, .. 192 -> 6, .. 224 -> 7)
+      t.bf = true; t.nct = (g.KH + 15) / 16; t.mode = 6; t.usig = true;
+      t.lds = std::max(pair_worker_bytes(t.nct, g.NS2, g.Q, g.C), pair_folder_bytes(g.B, g.chain_kw));
+    } else {
+      t.bf = image_bytes_bf(g.NCT, g.NS2) + rest + FOLD_LDS_SLACK <= FOLD_LDS_BYTES && bf_fits(g, rest, 1);
+      if (t.bf && g.usig && !g.r_store) t.mode = 5;      // the variant without R stores: split-bf16 build only
+    }
+  } else if (kind == TileKind::Update) {
+    const long long tiles = ((long long)g.n / (g.nb > 0 ? g.nb : 1) + 15) / 16 + (long long)g.Q + 1;
+    const int wpb = g.upd_threads / 64;
+    blocks = ((tiles + g.upd_tpw - 1) / g.upd_tpw + wpb - 1) / wpb;
+    if (blocks > g.upd_maxblocks) blocks = g.upd_maxblocks;   // resident capacity (workgroups per CU x CUs)
+    if (blocks > g.nwmax / wpb) blocks = g.nwmax / wpb;
+    if (blocks < 1) blocks = 1;
+    rest = fold_table_bytes(g.B, g.K, g.Q, g.C, g.fused_fold != 0, g.pen_lds != 0, true);
+    t.bf = bf_fits(g, rest, blocks);
+    if (g.upd_wps == 4) { t.wps = 4; t.usig = true; t.threads = 1024; }   // plan_shape: upd_threads == 1024, uniform sigma, K <= 64
+    else { t.usig = g.usig != 0; t.threads = g.upd_threads; }
+  } else {
+    // MFMA tile passes over the static 16-cell tiles (head, Lloyd, seeding race): 256-thread workgroups, capped at one resident generation --
+    // measured: 768-thread workgroups (one per CU) are 30% slower (tail effect)
+    const bool lloyd = kind == TileKind::Lloyd;
+    const int wpb = 256 / 64;
+    blocks = (((long long)g.ntitems + g.upd_tpw - 1) / g.upd_tpw + wpb - 1) / wpb;
+    if (blocks > g.nwmax / wpb) blocks = g.nwmax / wpb;
+    if (g.static_maxblocks > 0 && blocks > g.static_maxblocks) blocks = g.static_maxblocks;      // (seeding with three workgroups per CU -- 166 registers would allow it -- measured: no gain, 1.53 / 1.55 ms of k-means initialisation)
+    rest = lloyd ? lloyd_sum_bytes(g.K, g.d) : 0;
+    if (lloyd && blocks > 512) blocks = 512;
+    if (blocks < 1) blocks = 1;
+    t.threads = 256; t.bf = bf_fits(g, rest, blocks) || (lloyd && bf_fits(g, rest, 256));
+    // Lloyd with the larger image: two 256-thread workgroups per CU no longer fit next to their K x d sum tables -> one of 512 threads
+    if (t.bf && lloyd && !bf_fits(g, rest, blocks)) {
+      t.threads = 512; blocks = (blocks + 1) / 2; if (blocks > 256) blocks = 256;
+      // one workgroup per CU (image + K x d sum table: 84 KB): THREE waves per SIMD -- the kernel needs 150 registers, and the MFMA chain, the
+      // arg-min and the LDS sums of a tile run one after the other on one accumulator set: a third wave fills the gaps (round 6: 0.13 ms of 1.69 per
+      // k-means initialisation at 1M cells against two waves per SIMD)
+      if (g.NCT >= 5 && g.NCT <= 7) { t.wps = 3; t.threads = 768; }
+    }
+    // head variants: general sigma | uniform sigma | uniform sigma at 4 waves per SIMD (K <= 64)
+    if (kind == TileKind::Head) { if (g.upd_wps == 4) { t.wps = 4; t.usig = true; } else t.usig = g.usig != 0; }
+  }
+  if (t.mode != 6) t.lds = (t.bf ? image_bytes_bf(g.NCT, g.NS2) : image_bytes_f32(g.NQ, g.NS)) + rest;
+  t.blocks = (int)blocks; t.valid = t.lds <= LDS_PER_CU && t.blocks >= 1;
+  return t;
 }
 
 }  // namespace hmx

@@ -37,7 +37,10 @@ extern "C" {
  *   "objslots" (slot rows of a round's objective partials: min(n_blocks, 64)), "upd_contig" (launch-per-step path: contiguous tile ranges per
  *   wave), "moe_mfma" (MFMA ridge kernels; 0: the first-generation ones);
  *   counters since hmx_setup: "carried_rounds" (rounds whose old contributions came from the round before, no pass over R), "rounds_without_R"
- *   (rounds whose R rows were not stored), "chain_rounds" (rounds run by a persistent chain). */
+ *   (rounds whose R rows were not stored), "chain_rounds" (rounds run by a persistent chain);
+ *   the last k_tile launch of a kind as it ran (plan_tile_launch, harmony_amd/csrc/hmx_plan.h): "launch:head" "launch:lloyd" "launch:seed" "launch:update"
+ *   "launch:chain" -- 9 doubles: valid, bf (1: split-bf16 build), nct, mode, wps, usig (the instantiation k_tile<nct, mode, wps, usig>), threads, blocks,
+ *   lds (bytes); -1 while the handle has not made a launch of that kind since hmx_setup. */
 
 /* probes of the R-compatible stream (host only, no device needed; used by the CPU tests) */
 void hmx_r_runif(uint32_t seed, int32_t n, double* out);            /* set.seed(seed); runif(n)                      */

@@ -1,5 +1,6 @@
 """The plan tests/test_plan_cpu.py checks on the CPU IS the plan the library runs: for shapes the suite sets up elsewhere, the path flags of a
-live handle equal what the probe of harmony_amd/csrc/hmx_plan.h returns for the same shape and the device's real CU count."""
+live handle equal what the probe of harmony_amd/csrc/hmx_plan.h returns for the same shape and the device's real CU count -- and every k_tile
+launch the handle then makes (hmx_get "launch:<kind>") is, field by field, the launch the probe plans for it."""
 import os
 import sys
 
@@ -7,18 +8,20 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from harmony_amd import Harmony, prepare_setup_args  # noqa: E402
+from harmony_amd import Harmony, HarmonyError, prepare_setup_args  # noqa: E402
 from helpers import synth  # noqa: E402
-from test_plan_cpu import plan  # noqa: E402
+from test_plan_cpu import LAUNCH_FIELDS, plan, tile_launch  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-CASES = {                               # N, d, levels, K, sigma
+CASES = {                               # N, d, levels, K, sigma[, environment]
     "uniform_K50": (30000, 50, (2,), 50, 0.1),
     "uniform_K100": (300000, 50, (10,), 100, 0.1),      # (20^2 blocks x 10 combinations x 64 <= N: old contributions carried, sort-free shuffle)
     "K200_three_covariates": (120000, 50, (4, 10, 20), 200, 0.1),
     "K_not_multiple_of_4": (20000, 30, (5,), 50 + 1, 0.1),
     "sigma_vector": (6000, 30, (4,), 40, "vector"),
+    "d68": (20000, 68, (4,), 100, 0.1),                 # (rows of 68 PCs: the split-bf16 form is not offered, every launch is of the fp32 build)
+    "uniform_K100_dot_f32": (300000, 50, (10,), 100, 0.1, {"HMX_DOT": "f32"}),
 }
 
 
@@ -26,18 +29,46 @@ CASES = {                               # N, d, levels, K, sigma
 def test_live_handle_runs_the_probed_plan(name, monkeypatch):
     for k in [k for k in os.environ if k.startswith("HMX_")]:
         monkeypatch.delenv(k)
-    N, d, levels, K, sigma = CASES[name]
+    N, d, levels, K, sigma = CASES[name][:5]
+    for k, v in (CASES[name][5] if len(CASES[name]) > 5 else {}).items():
+        monkeypatch.setenv(k, v)
     Z, meta, _ = synth(N, d=d, levels=levels, seed=7)
     skw, _ = prepare_setup_args(Z, meta, list(meta), nclust=K, sigma=np.linspace(0.08, 0.16, K) if sigma == "vector" else sigma)
+    skw["max_iter_kmeans"] = 2
     h = Harmony(seed=1)
     h.setup(**skw)                      # (no HMX_CHAIN_WGS: the chain's workgroup count "chain_wgs" is the device's CU count)
     phi_i, phi_p, _, B = skw["Phi"]
     C_ = len(levels)
     combos, counts = np.unique(np.asarray(phi_i).reshape(N, C_), axis=0, return_counts=True)      # (one level per covariate and cell, grouped by covariate)
-    p = plan(N, K, d=d, B=int(B), C_=C_, Q=len(combos), nb=int(h._scalar("n_blocks")), cells_per_block=int(h._scalar("cells_per_block")),
-             cus=int(h._scalar("chain_wgs")), usig=int(sigma != "vector"), ntitems=int(((counts + 15) // 16).sum()))
+    cus = int(h._scalar("chain_wgs"))
+    shape = dict(d=d, B=int(B), C_=C_, Q=len(combos), nb=int(h._scalar("n_blocks")), cells_per_block=int(h._scalar("cells_per_block")),
+                 cus=cus, usig=int(sigma != "vector"), ntitems=int(((counts + 15) // 16).sum()))
+    p = plan(N, K, **shape)
     live = {g: int(h._scalar(g)) for g in ("chain", "chain_pair", "dot_bf", "sold_carry", "shuffle_inv", "usig", "upd_wps")}
     want = {"chain": int(p["chain_ok"] or p["chain_pair"]), "chain_pair": p["chain_pair"], "dot_bf": p["dot_bf"], "sold_carry": p["carry_ok"],
             "shuffle_inv": p["shuf_inv"], "usig": p["usig"], "upd_wps": p["upd_wps"]}
     print("PLAN", name, live)
     assert live == want, (name, live, p)
+
+    def ran(kind):
+        """the handle's last launch of a kind, or None where it made none"""
+        try:
+            return dict(zip(LAUNCH_FIELDS, (int(v) for v in h._get("launch:" + kind))))
+        except HarmonyError:
+            return None
+
+    assert all(ran(k) is None for k in ("head", "seed", "lloyd", "update", "chain")), "nothing is launched before init_cluster"
+    h.init_cluster_cpp()                # seeding race, ten Lloyd iterations, head
+    h.cluster_cpp()                     # head, two rounds
+    rounds = int(h._get("kmeans_rounds")[-1])
+    # what is set per launch, from the handle's own counters: the last round's launches stored their R rows unless every round of the call went
+    # without (the call's last round always stores); the fold is in the prologue of the chain, and of the update where the plan's path says so
+    r_store = 0 if int(h._scalar("rounds_without_R")) >= rounds else 1
+    on_chain = int(h._scalar("chain"))
+    got = {k: ran(k) for k in ("head", "seed", "lloyd", "update", "chain")}
+    print("LAUNCH", name, {"rounds": rounds, "rounds_without_R": int(h._scalar("rounds_without_R")), "r_store": r_store}, got)
+    for kind in ("head", "seed", "lloyd", "update", "chain"):
+        t = tile_launch(kind, N, K, workgroups=cus, r_store=r_store, **shape)
+        runs = t.pop("ran") and kind != ("update" if on_chain else "chain")
+        assert got[kind] == (t if runs else None), (name, kind, got[kind], t)
+    assert got["head"] and got["seed"] and (got["chain"] if on_chain else got["update"]), (name, got)

@@ -138,3 +138,133 @@ def test_forcing_switch_flips_the_decision_it_documents(monkeypatch, env, shape,
         monkeypatch.setenv(k, v)
     forced = plan(**shape)
     assert {k: (base[k], forced[k]) for k in diff(base, forced)} == flips
+
+
+# ---- one k_tile launch (plan_tile_launch): which instantiation, of which build, on what grid, with how much LDS -------------------------------
+KINDS = {"update": 0, "head": 1, "lloyd": 2, "seed": 3, "chain": 4}
+LAUNCH_FIELDS = ("valid", "bf", "nct", "mode", "wps", "usig", "threads", "blocks", "lds")
+KB = 1024
+
+
+def shape_vector(N, K, d=50, B=20, C_=1, Q=None, nb=20, **kw):
+    s = dict(N=N, N_global=N, d=d, K=K, B=B, C=C_, Q=B if Q is None else Q, nb=nb, cells_per_block=max(1, N // nb), world=1, sharded=0, cus=256, usig=1,
+             ridge_arith=0, oe_arith=0, obj_arith=0, solve_arith=0, tun_wps=-1, tun_tpw=-1, grid=2048, ntitems=(N + 15) // 16)
+    assert not set(kw) - set(s), kw
+    s.update(kw)
+    return (C.c_longlong * len(PLAN_SHAPE))(*[int(s[k]) for k in PLAN_SHAPE])
+
+
+def tile_launch(kind, N, K, workgroups=256, r_store=1, fused_fold=-1, **kw):
+    """the launch of one kind for a shape, as a dict of LAUNCH_FIELDS + "ran" (0: the library makes no such launch for the shape); None: plan limit.
+    fused_fold -1: as the unsharded plan's path says (the chain folds, the update does off the chain where the tables fit)"""
+    lib = plan_probe()
+    lib.probe_tile_launch.argtypes = [C.POINTER(C.c_longlong), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_longlong)]
+    out = (C.c_longlong * 10)()
+    if lib.probe_tile_launch(shape_vector(N, K, **kw), KINDS[kind], workgroups, r_store, fused_fold, out):
+        return None
+    return dict(zip(("ran",) + LAUNCH_FIELDS, out))
+
+
+def launch(bf, nct, mode, wps, usig, threads, blocks, lds, ran=1):
+    return dict(ran=ran, valid=1, bf=bf, nct=nct, mode=mode, wps=wps, usig=usig, threads=threads, blocks=blocks, lds=lds)
+
+
+def test_headline_shape_launches():
+    """K = 100, d = 50, 20 batches, 1M cells: NCT = 7 cluster tiles, rows of zs = 52 floats -> NS2 = 2 steps of 32 PCs: split image 7 * 2 * 3 KB = 42 KB"""
+    img = 7 * 2 * 3 * KB
+    # chain: O' int64 [20][100] + penalties fp32 [2000] + levels [20][1]; image + tables + 64 <= 150 KB and one workgroup per CU: split-bf16 build,
+    # one workgroup of 512 threads per CU; rounds whose R rows nobody reads run MODE 5
+    fold = 20 * 100 * 8 + (2000 + 20 * 1) * 4
+    assert tile_launch("chain", 1000000, 100, r_store=0) == launch(1, 7, 5, 2, 1, 512, 256, img + fold)
+    assert tile_launch("chain", 1000000, 100, r_store=1) == launch(1, 7, 4, 2, 1, 512, 256, img + fold)
+    # static tiles: 62 500 tiles / 4 waves = 15 625 workgroups, capped at nwmax / 4 = 2048 and at static_maxblocks = 512 (NCT >= 5): two per CU, 2 * 42 KB fit
+    assert tile_launch("head", 1000000, 100) == launch(1, 7, 1, 2, 1, 256, 512, img)
+    assert tile_launch("seed", 1000000, 100) == launch(1, 7, 3, 2, 0, 256, 512, img)
+    # Lloyd: int64 sums [100][50] + counts [100]; two workgroups per CU would need 2 * (42 KB + 40 800) > 160 KB, one fits: one of 512 threads on half
+    # the grid -- and, for 5 .. 7 cluster tiles, three waves per SIMD: 768 threads
+    sums = (100 * 50 + 100) * 8
+    assert 2 * (img + sums) > 160 * KB >= img + sums
+    assert tile_launch("lloyd", 1000000, 100) == launch(1, 7, 2, 3, 0, 768, 256, img + sums)
+
+
+def test_update_launches_K64_and_configs4():
+    # K = 64: NCT = 4, split image 4 * 2 * 3 KB; block of 50 000 cells: 3125 tiles + 20 combinations + 1 = 3146; fold in the prologue (fused_fold = 1):
+    # O' [20][64] int64 + penalties [1280] + levels [20]
+    img, fold = 4 * 2 * 3 * KB, 20 * 64 * 8 + (1280 + 20) * 4
+    # uniform sigma: four waves per SIMD, 1024 threads = 16 waves per workgroup: ceil(3146 / 16) = 197 workgroups (< 256 resident, < nwmax / 16 = 512)
+    assert tile_launch("update", 1000000, 64, fused_fold=1) == launch(1, 4, 0, 4, 1, 1024, 197, img + fold)
+    # vector sigma: two waves per SIMD, 512 threads = 8 waves: ceil(3146 / 8) = 394, capped at upd_maxblocks = 256
+    assert tile_launch("update", 1000000, 64, fused_fold=1, usig=0) == launch(1, 4, 0, 2, 0, 512, 256, img + fold)
+    # K = 200, B = 200, three covariates, 200 combinations at 1M cells: the wave-pair chain, halves of KH = 100 clusters = 7 cluster tiles each.
+    # workers: both halves' images 2 * 7 * 2 * 3 KB + levels [200][3] + exchange slots 4 * 2 * 2 * 16 * 8 + log2 penalties [8][4][16][7] fp32;
+    # folders (20 clusters each): O slice + deltas [2][200][20] + masses [20], int64
+    lds_w, lds_f = 2 * 7 * 2 * 3 * KB + 600 * 4 + 4 * 2 * 2 * 16 * 8 + 8 * 4 * 16 * 7 * 4, (2 * 200 * 20 + 20) * 8
+    assert (lds_w, lds_f) == (104800, 64160) and plan(1000000, **C4)["KH"] == 100
+    assert tile_launch("chain", 1000000, r_store=0, **C4) == launch(1, 7, 6, 2, 1, 512, 256, max(lds_w, lds_f))
+    # the same at 5M cells: launch per step, NCT = 13, no table in LDS (200 * 200 * 4 > 24 KB: pen_lds = 0; no fold in the prologue): the image alone;
+    # 15 625 tiles + 201 over 8 waves -> capped at 256
+    t = tile_launch("update", 5000000, **C4)
+    assert t == launch(1, 13, 0, 2, 1, 512, 256, 13 * 2 * 3 * KB) and tile_launch("chain", 5000000, **C4)["ran"] == 0
+
+
+def test_fp32_build_where_the_split_form_is_not_offered(monkeypatch):
+    fold, sums = 20 * 100 * 8 + (2000 + 20) * 4, (100 * 50 + 100) * 8
+    # d = 68: zs = 68 -> NT4 = 4, NS2 = 3: dot_bf = 0; fp32 image [NQ = 2][NS = 17] KB; the chain has no variant without R stores there
+    img = 2 * 17 * KB
+    assert tile_launch("chain", 1000000, 100, d=68, r_store=0) == launch(0, 7, 4, 2, 1, 512, 256, img + fold)
+    assert tile_launch("head", 1000000, 100, d=68) == launch(0, 7, 1, 2, 1, 256, 512, img)
+    # HMX_DOT=f32 at d = 50: fp32 image [2][13] KB; Lloyd keeps two 256-thread workgroups per CU
+    monkeypatch.setenv("HMX_DOT", "f32")
+    img = 2 * 13 * KB
+    assert tile_launch("chain", 1000000, 100, r_store=0) == launch(0, 7, 4, 2, 1, 512, 256, img + fold)
+    assert tile_launch("lloyd", 1000000, 100) == launch(0, 7, 2, 2, 0, 256, 512, img + sums)
+    assert tile_launch("update", 1000000, 64, fused_fold=1) == launch(0, 4, 0, 4, 1, 1024, 197, 1 * 13 * KB + 20 * 64 * 8 + (1280 + 20) * 4)
+
+
+def resource_table_k_tile():
+    """{(bf, nct, mode, wps, usig)} of the k_tile rows of profiles/r6_kernel_resources.txt: bf build in hmx_tile_bf, fp32 build in hmx_kernels"""
+    import re
+    rows = set()
+    for line in open(os.path.join(ROOT, "profiles", "r6_kernel_resources.txt")):
+        m = re.match(r"(hmx_\w+)\s.*\sk_tile<(\d+), (\d+), (\d+), (true|false), (true|false)>$", line.rstrip())
+        if m:
+            bf = int(m.group(6) == "true")
+            assert m.group(1) == ("hmx_tile_bf" if bf else "hmx_kernels"), line
+            rows.add((bf, int(m.group(2)), int(m.group(3)), int(m.group(4)), int(m.group(5) == "true")))
+    return rows
+
+
+def test_every_planned_launch_of_the_envelope_is_a_kernel_of_the_build(monkeypatch):
+    """Every launch the plan makes across the envelope is valid, within a CU's LDS, of a workgroup size the kernels are built for, and names an
+    instantiation that the build has (profiles/r6_kernel_resources.txt) in the object of its build.  No allowance."""
+    import numpy as np
+    lib = plan_probe()
+    lib.probe_tile_sweep.argtypes = [C.POINTER(C.c_longlong), C.c_int, C.POINTER(C.c_longlong)]
+    table = resource_table_k_tile()
+    assert len(table) == 214
+    key = lambda bf, nct, mode, wps, usig: (((bf * 32 + nct) * 8 + mode) * 8 + wps) * 2 + usig      # noqa: E731
+    known = np.array(sorted(key(*r) for r in table))
+    reached, n, buf = set(), 0, (C.c_longlong * (256 * 5 * 10))()
+    for dot in (None, "f32"):
+        if dot:
+            monkeypatch.setenv("HMX_DOT", dot)
+        for d in (1, 16, 50, 64, 68, 76, 100, 128):
+            for B, C_, Q in ((2, 1, 2), (20, 1, 20), (200, 3, 200)):
+                for nb in (1, 20, 64):
+                    for usig in (0, 1):
+                        for N in (2000, 1000000, 20000000):
+                            for r_store in (0, 1):
+                                lib.probe_tile_sweep(shape_vector(N, 1, d=d, B=B, C_=C_, Q=Q, nb=nb, usig=usig), r_store, buf)      # every K in 1 .. 256, all five kinds
+                                a = np.frombuffer(buf, dtype=np.int64).reshape(256 * 5, 10)
+                                a = a[a[:, 0] == 1]                                       # launches the library makes (plan admitted, kind on the shape's path)
+                                ran, valid, bf, nct, mode, wps, us, threads, blocks, lds = a.T
+                                k = key(bf, nct, mode, wps, us)
+                                ok = (valid == 1) & (lds <= 160 * KB) & np.isin(threads, (256, 512, 768, 1024)) & (blocks >= 1) & np.isin(k, known)
+                                assert ok.all(), (dot, d, B, nb, usig, N, r_store, a[~ok][:5])
+                                n += len(a)
+                                reached.update(np.unique(k).tolist())
+    unreached = sorted(r for r in table if key(*r) not in reached)
+    print("planned launches checked: %d; k_tile rows of the table no swept shape reaches (%d of %d):" % (n, len(unreached), len(table)))
+    for bf, nct, mode, wps, usig in unreached:
+        print("  %s k_tile<%d, %d, %d, %s, %s>" % ("hmx_tile_bf" if bf else "hmx_kernels", nct, mode, wps, str(bool(usig)).lower(), str(bool(bf)).lower()))
+    assert n > 1000000

@@ -7,6 +7,7 @@
 #include "hmx_internal.h"
 #include "hmx_rrng.h"
 #include "hmx_plan.h"
+#include "hmx_round.h"
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>
@@ -208,7 +209,6 @@ int hmx_comm_allreduce_host(hmx_ctx* ctx, double* inout, int32_t count, int32_t 
   RcclApi* api = rccl_api(nullptr);
   if (ctx->device >= 0) HIPCHK(hipSetDevice(ctx->device));
   if (!ctx->L.stream) { HIPCHK(hipStreamCreateWithFlags(&ctx->L.stream, hipStreamNonBlocking)); ctx->own_stream = true; }
-  if (ctx->side) HIPCHK(hipStreamSynchronize(ctx->side));
   double* d = nullptr;
   HIPCHK(hipMalloc((void**)&d, sizeof(double) * (size_t)count));
   hipError_t e = hipMemcpyAsync(d, inout, sizeof(double) * (size_t)count, hipMemcpyHostToDevice, ctx->L.stream);
@@ -229,7 +229,7 @@ int hmx_restart(hmx_ctx* ctx) {
   HIPCHK(hipSetDevice(ctx->device));
   const Dev& D = ctx->D;
   l_normalize_from(ctx->L, D.Zo, D.Zc, D.n, D.d, D.zs); KCHK();  // Z_corr = normalise(Z_orig) :42 (one pass)
-  for (int i = 0; i < 2; i++) if (ctx->sold_state[i] == 2) ctx->sold_state[i] = 1;
+  ctx->ledger.restart();      // (R is rewritten, and no order set is taken for sorted)
   HIPCHK(hipStreamSynchronize(ctx->L.stream));
   ctx->obj_pending = 0; ctx->obj_harmony_pending = false;
   ctx->obj_kmeans.clear(); ctx->obj_dist.clear(); ctx->obj_entropy.clear(); ctx->obj_cross.clear(); ctx->obj_harmony.clear();
@@ -238,8 +238,6 @@ int hmx_restart(hmx_ctx* ctx) {
   ctx->obj_warm = ctx->rg_warm = ctx->rp_warm = false;            // (a run never depends on what the handle computed before it)
   ctx->head_is_stale = false;
   HIPCHK(hipMemsetAsync(ctx->D.solve_err, 0, sizeof(int), ctx->L.stream));
-  if (ctx->side) HIPCHK(hipStreamSynchronize(ctx->side));
-  for (int i = 0; i < 4; i++) ctx->sorted_round[i] = -1;      // (sorted_on_side stays: a sort still running on the side stream is waited for before its set is reused)
   return 0;
 }
 

@@ -161,9 +161,8 @@ int64_t hmx_get(hmx_ctx* ctx, const char* field, double* out, int64_t cap) {
   if (f == "prof:update_launches") return scalar((double)ctx->prof_update_launches);
   if (f == "prof:update_cells") return scalar((double)ctx->prof_update_cells);
   if (f == "prof:update_steps") return scalar((double)ctx->prof_update_steps);
-  if (f == "sync") {        // everything queued on the handle's streams has completed (hosts without a HIP runtime of their own: bench.py --bootstrap file)
+  if (f == "sync") {        // everything queued on the handle's stream has completed (hosts without a HIP runtime of their own: bench.py --bootstrap file)
     if (ctx->L.stream && hipStreamSynchronize(ctx->L.stream) != hipSuccess) return -1;
-    if (ctx->side && hipStreamSynchronize(ctx->side) != hipSuccess) return -1;
     return scalar(1.0);
   }
   if (f == "chain") return scalar((ctx->chain_ok || ctx->D.chain_pair) ? 1.0 : 0.0);
@@ -180,6 +179,11 @@ int64_t hmx_get(hmx_ctx* ctx, const char* field, double* out, int64_t cap) {
       return vec(std::vector<double>{(double)t.valid, (double)t.bf, (double)t.nct, (double)t.mode, (double)t.wps, (double)t.usig, (double)t.threads, (double)t.blocks, (double)t.lds});
     }
     return -1;      // (no such kind, or no launch of it on this handle yet)
+  }
+  if (f == "round:last") {      // the plan of the last round of update_R (hmx_round.h): path, merged, chain_tail, carried, write_next, r_store, closing form, exchanges
+    if (!ctx->round_seen) return -1;
+    const RoundPlan& r = ctx->last_round;
+    return vec(std::vector<double>{(double)r.path, (double)r.merged, (double)r.chain_tail, (double)r.carried, (double)r.write_next, (double)r.r_store, (double)r.close, (double)r.exchanges});
   }
   // further values of the launch plan (hmx_plan.h) as hmx_setup took them, for tests that claim a path
   if (f == "need_lorder") return scalar((double)ctx->D.need_lorder);     // the shuffle also writes lorder / lcombo (k_oldsum's gather variant reads them)

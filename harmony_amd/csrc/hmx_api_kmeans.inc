@@ -119,9 +119,8 @@ int kmeans_centers(hmx_ctx* ctx) {
 void apply_set(Dev& D, const hmx_ctx::SortSet& s) {
   D.blk = s.blk; D.lorder = s.lorder; D.lpair = s.lpair; D.lcombo = s.lcombo; D.boff = s.boff; D.binoff = s.binoff; D.counts = s.counts; D.offs = s.offs; D.blkv = s.blkv; D.bincnt = s.bincnt;
 }
-// ---- sort_sched = 3 -----------------------------------------------------------------------------------------------------------
 // rounds first..(first | 3) in one batch of launches on the main stream, into sets round & 3.
-// (Sorting a group AHEAD on the side stream was measured twice and lost twice: next to the persistent block chain every block step got
+// (Sorting a group AHEAD on a side stream was measured twice and lost twice: next to the persistent block chain every block step got
 //  1 us slower (14.2 vs 14.1 ms per run); in the shadow of the correction's statistics pass that pass went from 1.47 to 2.25 ms per run for
 //  0.5 ms of sort taken off the main stream.  The sort's thousands of one-wave workgroups get in the way of whatever runs beside them.)
 int sort_group(hmx_ctx* ctx, uint64_t first) {
@@ -143,67 +142,36 @@ int sort_group(hmx_ctx* ctx, uint64_t first) {
   }
   l_sort_batch(ctx->L, Dt, Sb, nr, ctx->seed, first, (uint64_t)ctx->N_global, (uint64_t)ctx->goff, ctx->cells_per_block); KCHK();
   }
-  for (int r = 0; r < nr; r++) {
-    const int os = (int)((first + (uint64_t)r) & 3);
-    ctx->sorted_round[os] = (int64_t)first + r; ctx->sorted_seed[os] = ctx->seed; ctx->sorted_nxt[os] = Dt.nxt != 0; ctx->sorted_on_side[os] = false;
-  }
+  for (int r = 0; r < nr; r++) ctx->ledger.sorted(first + (uint64_t)r, ctx->seed, Dt.nxt != 0);
   return 0;
 }
 int prepare_round(hmx_ctx* ctx, uint64_t round) {
   Dev& D = ctx->D;
-  const int sset = (int)(round & (uint64_t)ctx->oset_mask);
-  const bool host_order = !ctx->injected.empty() || ctx->rng_mode == 1;
-  if (ctx->sort_sched == 3 && !host_order) {
-    if (!(ctx->sorted_round[sset] == (int64_t)round && ctx->sorted_seed[sset] == ctx->seed)) CHK(sort_group(ctx, round));    // this round and the rest of its group
-    apply_set(D, ctx->sets[sset]);
-    D.nxt = ctx->sorted_nxt[sset] ? 1 : 0;
+  apply_set(D, ctx->sets[round & 3]);
+  if (ctx->injected.empty() && ctx->rng_mode != 1) {
+    if (!ctx->ledger.is_order(round, ctx->seed)) CHK(sort_group(ctx, round));    // this round and the rest of its group
+    D.nxt = ctx->ledger.keyed_by_next(round) ? 1 : 0;
     return 0;
   }
-  if (ctx->sorted_on_side[sset]) {   // a prefetch into this set is (or was) in flight on the side stream: order the main stream behind it
-    HIPCHK(hipStreamWaitEvent(ctx->L.stream, ctx->ev_sorted[sset], 0));
-    ctx->sorted_on_side[sset] = false;
-  }
-  apply_set(D, ctx->sets[sset]);
-  const bool have = !host_order && ctx->sorted_round[sset] == (int64_t)round && ctx->sorted_seed[sset] == ctx->seed;
-  auto prefetch_next = [&]() -> int {   // round + 1 into the other set, on the side stream, behind everything that still reads that set
-    if (!ctx->sort_overlap || host_order || !ctx->side) return 0;
-    const int t = sset ^ 1;
-    if (ctx->sorted_round[t] == (int64_t)round + 1 && ctx->sorted_seed[t] == ctx->seed) return 0;     // (second call for this round)
-    HIPCHK(hipEventRecord(ctx->ev_free[t], ctx->L.stream));
-    HIPCHK(hipStreamWaitEvent(ctx->side, ctx->ev_free[t], 0));
-    Dev Dt = D; apply_set(Dt, ctx->sets[t]);
-    Dt.nxt = ctx->carry_ok ? 1 : 0;
-    Launch L2 = ctx->L; L2.stream = ctx->side;
-    l_sort_blocks(L2, Dt, true, ctx->seed, round + 1, (uint64_t)ctx->N_global, (uint64_t)ctx->goff, ctx->cells_per_block); KCHK();
-    HIPCHK(hipEventRecord(ctx->ev_sorted[t], ctx->side));
-    ctx->sorted_round[t] = (int64_t)round + 1; ctx->sorted_seed[t] = ctx->seed; ctx->sorted_on_side[t] = true; ctx->sorted_nxt[t] = Dt.nxt != 0;
-    return 0;
-  };
-  if (have) return prefetch_next();
-  ctx->sorted_round[sset] = -1;
-  bool gen_blocks = false;
-  if (ctx->injected.empty() && ctx->rng_mode == 1) {   // update_order = shuffle(linspace(0, N-1, N)) from R's stream (:272-273)
+  ctx->ledger.lost(round);      // the host owns this round's shuffle: its order goes into the round's set, keyed by the block alone
+  if (ctx->injected.empty()) {   // update_order = shuffle(linspace(0, N-1, N)) from R's stream (:272-273)
     ensure_rrng(ctx);
     std::vector<int64_t> order;
     ctx->rrng.arma_shuffle(ctx->N_global, order);
     ctx->injected.push_back(std::move(order));
   }
-  if (!ctx->injected.empty()) {  // host-provided shuffle: block(g) from its position
-    std::vector<int64_t> order = std::move(ctx->injected.front());
-    ctx->injected.pop_front();
-    std::vector<int> pos_blk((size_t)ctx->N);
-    std::vector<int64_t> pos((size_t)ctx->N_global);
-    for (int64_t p = 0; p < ctx->N_global; p++) pos[(size_t)order[p]] = p;
-    for (int64_t i = 0; i < ctx->N; i++) {
-      uint64_t b = (uint64_t)pos[(size_t)(ctx->goff + ctx->perm[i])] / ctx->cells_per_block;
-      pos_blk[i] = (int)std::min<uint64_t>(b, (uint64_t)(ctx->nb - 1));
-    }
-    CHK(h2d(ctx, D.blk, pos_blk.data(), pos_blk.size()));
-    ctx->injected_round = (int64_t)round;
-  } else gen_blocks = true;   // block ids from the Feistel bijection, computed inside the sort's histogram kernel
-  D.nxt = (gen_blocks && ctx->carry_ok) ? 1 : 0;
-  l_sort_blocks(ctx->L, D, gen_blocks, ctx->seed, round, (uint64_t)ctx->N_global, (uint64_t)ctx->goff, ctx->cells_per_block); KCHK();
-  ctx->sorted_nxt[sset] = D.nxt != 0;
-  if (gen_blocks) { ctx->sorted_round[sset] = (int64_t)round; ctx->sorted_seed[sset] = ctx->seed; }
-  return prefetch_next();
+  std::vector<int64_t> order = std::move(ctx->injected.front());      // block(g) from its position
+  ctx->injected.pop_front();
+  std::vector<int> pos_blk((size_t)ctx->N);
+  std::vector<int64_t> pos((size_t)ctx->N_global);
+  for (int64_t p = 0; p < ctx->N_global; p++) pos[(size_t)order[p]] = p;
+  for (int64_t i = 0; i < ctx->N; i++) {
+    uint64_t b = (uint64_t)pos[(size_t)(ctx->goff + ctx->perm[i])] / ctx->cells_per_block;
+    pos_blk[i] = (int)std::min<uint64_t>(b, (uint64_t)(ctx->nb - 1));
+  }
+  CHK(h2d(ctx, D.blk, pos_blk.data(), pos_blk.size()));
+  ctx->injected_round = (int64_t)round;
+  D.nxt = 0;
+  l_sort_blocks(ctx->L, D); KCHK();
+  return 0;
 }

@@ -396,8 +396,7 @@ int update_R_ref(hmx_ctx* ctx) {
     //  objective left the library's stream, with the library's stream at the highest priority as well: 71.9 / 72.6 ms against 70.5 / 71.4 in line.)
     CHK(objective_snapshot(ctx)); }
   CHK(push_objective(ctx));
-  ctx->sets_clean = false;
-  for (int i = 0; i < 2; i++) if (ctx->sold_state[i] == 2) ctx->sold_state[i] = 1;
+  ctx->ledger.sets_used(); ctx->ledger.r_rewritten();
   if (ctx->profile) ctx->prof_update_cells += ctx->N;
   ctx->R_valid = true;
   ctx->timers["update_R"] += now_ms() - t0;

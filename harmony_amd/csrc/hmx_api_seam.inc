@@ -219,12 +219,13 @@ struct hmx_ctx {
   // profiling of the dominant kernel
   int profile = 0;             // 0 off | 1 the dominant kernel's launches carry a start / stop event pair | 2 and every phase is bracketed by events (PhaseScope)
   bool fused_ok = false;       // k_tile prologue fold usable (LDS budget) and not disabled
-  // Old-contribution tables: two buffers.  `cur` is what this round's block steps subtract; the other one collects, inside this
+  // Old-contribution tables: two buffers.  ledger.cur is what this round's block steps subtract; the other one collects, inside this
   // round's tile kernels, the old contributions of the NEXT round's blocks (carry_ok: the shuffle keys every tile by its cells'
-  // next block) -- then the next round needs no pass over R (k_oldsum).  state: 0 all zero, 1 unknown contents, 2 carried for round sold_round.
-  long long* sold_buf[2] = {nullptr, nullptr}; int sold_cur = 0, sold_state[2] = {1, 1}; int64_t sold_round[2] = {-1, -1}; uint64_t sold_seed[2] = {0, 0};
-  bool sets_clean = false;     // the three Snew replica sets are all zero
-  bool carry_ok = false, last_round_hint = false, round_may_be_last = true; bool sorted_nxt[4] = {};
+  // next block) -- then the next round needs no pass over R (k_oldsum).  What the tables, the order sets and the replica sets hold: the ledger (hmx_round.h).
+  long long* sold_buf[2] = {nullptr, nullptr}; RoundLedger ledger;
+  bool carry_ok = false, last_round_hint = false, round_may_be_last = true;
+  int fold_impl = 0;           // Switches::fold_impl, read at setup
+  RoundPlan last_round; bool round_seen = false;      // the plan of the last round of update_R (hmx_get "round:last")
   // R rows that nobody reads are not stored (Dev::r_store = 0: the head inside cluster_cpp, rounds that cannot be a call's last).  R_valid says
   // whether D.R holds the rows of the LAST head / round: cleared when a pass starts, set when a storing pass has been queued completely.  A call
   // that fails half way leaves it false, and the getters / the correction refuse to consume stale rows.  r_store_always: HMX_R_STORE=1, read at setup.
@@ -242,18 +243,12 @@ struct hmx_ctx {
   double prof_update_ms = 0; int64_t prof_update_launches = 0, prof_update_cells = 0, prof_update_steps = 0;
   bool chain_check = false;    // a persistent-chain launch has run since the error word was last read
   // The round's shuffle (counting sort by block) touches no algorithmic state, and with the counter-based generator it depends
-  // on (seed, round) only: the sort of round r+1 runs on a SIDE stream while round r's old-sum pass streams on the main one,
-  // into the second of two buffer sets.
+  // on (seed, round) only: the shuffles of FOUR consecutive rounds run in one set of launches on the main stream (l_sort_batch / l_shuffle_inv),
+  // into four full order sets (round & 3) -- rounds keep their numbers across cluster_cpp calls, so a batch serves whichever calls its rounds
+  // fall into; between two block chains of a batch there is no sort kernel and no event at all.  The batches are aligned groups (round >> 2).
+  // A host-provided order is sorted on its own into its round's set.  (Sorting ahead on a side stream was measured and lost twice: DESIGN 4.5.)
   struct SortSet { int* blk; int* lorder; int2* lpair; int* lcombo; int* boff; int* binoff; int* counts; int* offs; int* blkv; int* bincnt; };
-  SortSet sets[4] = {}; int oset_mask = 1;      // order sets: round & oset_mask (two; four with the batched shuffle, sort_sched = 3)
-  hipStream_t side = nullptr; hipEvent_t ev_sorted[2] = {nullptr, nullptr}, ev_free[2] = {nullptr, nullptr};
-  int64_t sorted_round[4] = {-1, -1, -1, -1}; uint64_t sorted_seed[4] = {}; bool sorted_on_side[4] = {}; bool sort_overlap = true;
-  int sort_sched = 3;
-  // sort_sched = 3 (default): the shuffles of FOUR consecutive rounds in one set of launches on the main stream (l_sort_batch / l_shuffle_inv), into four full order
-  // sets -- rounds keep their numbers across cluster_cpp calls, so a batch serves whichever calls its rounds fall into; between two block
-  // chains of a batch there is no sort kernel and no event at all.  The batches are aligned groups (round >> 2).  sort_sched = 1: round 3's
-  // schedule (the whole sort of round r + 1 on the side stream behind chain r; also what host-provided orders use).  (A schedule in between --
-  // histogram halves rounds ahead on the side stream, the dependent tail on the main stream behind the chain -- was built and superseded: DESIGN 4.5.)
+  SortSet sets[4] = {};
   // the sort-free form of the batched shuffle (k_shuf_*): position -> (cell, rank) per order set, the blocks of the round behind a batch,
   // the (block, bin, part) count matrix
   bool shuf_inv = false; int2* posr[4] = {}; int* shuf_partcnt[4] = {}; int* shuf_binacc[4] = {}; int64_t injected_round = -1;   // (injected_round: the round whose order the host provided -- its D.blk came with it)
@@ -289,12 +284,7 @@ void free_all(hmx_ctx* ctx) {
   ctx->ev_pool.clear(); ctx->ev_used = 0;
   for (auto& e : ctx->ph_pool) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
   ctx->ph_pool.clear(); ctx->ph_used = 0;
-  if (ctx->side) { (void)hipStreamSynchronize(ctx->side); (void)hipStreamDestroy(ctx->side); ctx->side = nullptr; }
-  for (int i = 0; i < 2; i++) {
-    if (ctx->ev_sorted[i]) { (void)hipEventDestroy(ctx->ev_sorted[i]); ctx->ev_sorted[i] = nullptr; }
-    if (ctx->ev_free[i]) { (void)hipEventDestroy(ctx->ev_free[i]); ctx->ev_free[i] = nullptr; }
-  }
-  for (int i = 0; i < 4; i++) { ctx->sorted_round[i] = -1; ctx->sorted_on_side[i] = false; }
+  ctx->ledger.reset();
   {   // reference-arithmetic buffers (grown on demand, not in `allocs`)
     void* ps[] = {ctx->sq_start, ctx->sq_end, ctx->sq_total, ctx->sq_mismatch, ctx->headlist, ctx->roundlist, ctx->Of, ctx->Ef, ctx->Mtab, ctx->objT, ctx->objD,
                   ctx->inset, ctx->headq, ctx->obj_start, ctx->obj_partial, ctx->objf_slots, ctx->objf_stats, ctx->rg_totkl, ctx->rg_start, ctx->headlev, ctx->roundlev, ctx->pairlist, ctx->pair_idx, ctx->rg_tot, ctx->rp_tot, ctx->rp_start, ctx->plan_pair.d_segs, ctx->plan_pair.d_chains, ctx->plan_head.d_segs, ctx->plan_head.d_chains, ctx->plan_ridge.d_segs, ctx->plan_ridge.d_chains,
@@ -464,14 +454,9 @@ int objective_slot(hmx_ctx* ctx, double** slot) {     // next pinned host slot o
   return 0;
 }
 int push_objective(hmx_ctx* ctx) {
-  if (!ctx->h_obj) {
-    ctx->obj_cap = 64;
-    HIPCHK(hipHostMalloc((void**)&ctx->h_obj, sizeof(double) * 4 * ctx->obj_cap, hipHostMallocDefault));
-    std::memset(ctx->h_obj, 0, sizeof(double) * 4 * ctx->obj_cap);
-    HIPCHK(hipEventCreateWithFlags(&ctx->obj_event, hipEventDisableTiming));
-  }
-  if (ctx->obj_pending == ctx->obj_cap) CHK(flush_objectives(ctx));
-  HIPCHK(hipMemcpyAsync(ctx->h_obj + 4 * ctx->obj_pending, ctx->D.obj + 2, sizeof(double) * 4, hipMemcpyDeviceToHost, ctx->L.stream));   // dist, entropy, cross, chain error word
+  double* slot = nullptr;
+  CHK(objective_slot(ctx, &slot));
+  HIPCHK(hipMemcpyAsync(slot, ctx->D.obj + 2, sizeof(double) * 4, hipMemcpyDeviceToHost, ctx->L.stream));   // dist, entropy, cross, chain error word
   HIPCHK(hipEventRecord(ctx->obj_event, ctx->L.stream));
   ctx->obj_pending++;
   return 0;
@@ -482,36 +467,25 @@ int prepare_round(hmx_ctx* ctx, uint64_t round);
 int oe_head(hmx_ctx* ctx);
 int objective_snapshot(hmx_ctx* ctx, const Dev* Dterms = nullptr);
 int head_pass(hmx_ctx* ctx, bool normalise = false) {   // normalise: Z_corr <- normalise(Z_corr) first (:220)
-  // With the round-to-round carry (update_R) the head of cluster_cpp runs over the padded order of the round that FOLLOWS it and
-  // files its R sums as that round's old contributions: no pass over R between the head and the first round either.
-  const bool sharded_ = ctx->world > 1 || ctx->comm_force;
-  // (the head of init_cluster_cpp too: the first round then finds its old contributions filed as well -- no pass over R at all)
-  const bool gather = ctx->carry_ok && ctx->injected.empty() && ctx->rng_mode == 0;
-  if (gather) {
+  HeadIn in;      // the decisions: plan_head (hmx_round.h)
+  in.carry_ok = ctx->carry_ok; in.host_order = !ctx->injected.empty() || ctx->rng_mode != 0; in.normalise = normalise;
+  in.NT4 = ctx->D.NT4; in.NCT = ctx->D.NCT; in.upd_wps = ctx->D.upd_wps; in.max_iter_kmeans = ctx->max_iter_kmeans;
+  in.poll = ctx->poll != nullptr; in.r_store_always = ctx->r_store_always; in.seed = ctx->seed; in.round = (int64_t)ctx->round_counter;
+  if (head_gathers(in)) {
     PhaseScope ph(ctx, "randomize");
-    CHK(prepare_round(ctx, ctx->round_counter));     // (update_R finds this round sorted and the next one in flight)
+    CHK(prepare_round(ctx, ctx->round_counter));     // (update_R finds this round sorted)
   }
-  (void)sharded_;
   Dev D = ctx->D;
   ctx->head_is_stale = false;      // (dist_mat is recomputed here)
   ctx->objf_continued = true;      // (R is rewritten from the corrected embedding: the objective's warm starts are stale, its next evaluation takes a pass more up front)
-  // the register-pipelined head (two accumulator sets, rows of a tile in registers) normalises the rows it has loaded anyway
-  const bool fused_norm = normalise && D.NT4 <= 4 && D.NCT <= 7 && D.upd_wps != 4;
-  if (normalise && !fused_norm) { l_normalize(ctx->L, D.Zc, D.n, D.d, D.zs); KCHK(); }
-  D.head_norm = fused_norm ? 1 : 0;
-  for (int i = 0; i < 2; i++) if (ctx->sold_state[i] == 2) ctx->sold_state[i] = 1;     // R is rewritten: carried old contributions are void
-  D.head_gather = 0; D.Sold_head = nullptr;
-  void* zero_sold = nullptr; size_t n_sold = 0;
-  if (gather && ctx->sorted_nxt[ctx->round_counter & ctx->oset_mask] && ctx->sorted_round[ctx->round_counter & ctx->oset_mask] == (int64_t)ctx->round_counter) {
-    const int cur = ctx->sold_cur;
-    if (ctx->sold_state[cur] != 0) { zero_sold = ctx->sold_buf[cur]; n_sold = (size_t)D.nb * D.B * D.K; }      // (cleared with the three tables below: one launch)
-    D.head_gather = 1; D.Sold_head = ctx->sold_buf[cur];
-    ctx->sold_state[cur] = 2; ctx->sold_round[cur] = (int64_t)ctx->round_counter; ctx->sold_seed[cur] = ctx->seed;
-    // the head of cluster_cpp is followed, inside the same call, by a round that rewrites every R row and takes its old contributions from
-    // the sums filed here: the head's own rows are never read (Dev::r_store) -- 4K bytes per cell less.  (init_cluster_cpp's head is followed
-    // by the caller, who may read R: it stores.)
-    if (normalise && ctx->max_iter_kmeans >= 1 && !ctx->poll && !ctx->r_store_always) D.r_store = 0;
-  }
+  ctx->ledger.r_rewritten();
+  const HeadPlan hp = plan_head(in, ctx->ledger);
+  if (normalise && !hp.fused_norm) { l_normalize(ctx->L, D.Zc, D.n, D.d, D.zs); KCHK(); }
+  D.head_norm = hp.fused_norm ? 1 : 0;
+  D.head_gather = hp.files ? 1 : 0; D.Sold_head = hp.files ? ctx->sold_buf[ctx->ledger.cur] : nullptr; D.r_store = hp.r_store;
+  void* const zero_sold = hp.clear_first ? D.Sold_head : nullptr;      // (cleared with the three tables below: one launch)
+  const size_t n_sold = hp.clear_first ? (size_t)D.nb * D.B * D.K : 0;
+  if (hp.files) ctx->ledger.head_filed(in.round, in.seed);
   ctx->R_valid = false;
   // O, the contribution replicas, the objective slots (and a stale old-contribution table): ONE launch instead of three or four memsets
   l_zero4(ctx->L, D.O_fx, (size_t)D.B * D.K, D.Snew_fx, (size_t)D.nrep * D.B * D.K, D.objpart, 2 * (size_t)D.objslots * D.nwmax, zero_sold, n_sold); KCHK();

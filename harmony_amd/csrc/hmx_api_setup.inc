@@ -235,9 +235,8 @@ static int plan_device(hmx_ctx* ctx, const Design& G, Plan& P) {
   for (int g = 0; g < 8; g++) D.p2p_inbox[g] = ctx->p2p_peer[g];
   ctx->r_store_always = P.r_store_always; ctx->carry_ok = P.carry_ok; ctx->shuf_inv = P.shuf_inv; ctx->solve_on_device = P.solve_on_device;
   ctx->fused_ok = P.fused_ok; ctx->chain_ok = P.chain_ok; ctx->chain_wgs = P.chain_wgs;
-  ctx->oset_mask = 3; ctx->sort_overlap = true;      // four order sets: the batched shuffle (the per-round schedule lost round 4; its switches are gone)
   ctx->carried_rounds = 0; ctx->chain_rounds = 0; std::fill(ctx->tile_seen, ctx->tile_seen + 5, false); ctx->y_on_device = false; ctx->solve_pending = false;
-  ctx->sold_cur = 0; ctx->sold_state[0] = ctx->sold_state[1] = 1; ctx->sets_clean = false;
+  ctx->fold_impl = sw.fold_impl; ctx->ledger.reset(); ctx->round_seen = false;
   return 0;
 }
 
@@ -251,7 +250,7 @@ static int alloc_sort_set(hmx_ctx* ctx, const Plan& P, hmx_ctx::SortSet& t) {
   return 0;
 }
 
-// every device buffer of the handle (and the side stream / events of the shuffle), sized by the plan; buffers that must start zero are cleared here
+// every device buffer of the handle, sized by the plan; buffers that must start zero are cleared here
 static int alloc_device(hmx_ctx* ctx, const Plan& P, const Design& G) {
   Dev& D = ctx->D;
   hipStream_t st = ctx->L.stream;
@@ -280,14 +279,11 @@ static int alloc_device(hmx_ctx* ctx, const Plan& P, const Design& G) {
   HIPCHK(hipMemsetAsync(D.O_fx, 0, sizeof(long long) * BK, st)); HIPCHK(hipMemsetAsync(D.Snew_fx, 0, sizeof(long long) * D.nrep * BK, st));
   HIPCHK(hipMemsetAsync(D.O_alt, 0, sizeof(long long) * BK, st)); HIPCHK(hipMemsetAsync(D.Snew_alt, 0, sizeof(long long) * D.nrep * BK, st));
   HIPCHK(hipMemsetAsync(D.objpart, 0, sizeof(double) * 2 * (size_t)D.objslots * D.nwmax, st)); HIPCHK(hipMemsetAsync(D.obj, 0, sizeof(double) * 8, st));
-  // a round's shuffle: four order sets (set 0 is the one Dev starts on), a side stream for the overlapped shuffle of the next round, static sort chunks
+  // a round's shuffle: four order sets (set 0 is the one Dev starts on), static sort chunks
   for (int i = 0; i < 4; i++) CHK(alloc_sort_set(ctx, P, ctx->sets[i]));
   { const hmx_ctx::SortSet& t = ctx->sets[0];
     D.blk = t.blk; D.lorder = t.lorder; D.lpair = t.lpair; D.lcombo = t.lcombo; D.boff = t.boff; D.binoff = t.binoff; D.counts = t.counts; D.offs = t.offs; D.blkv = t.blkv; D.bincnt = t.bincnt; }
   CHK(dalloc(ctx, &D.schunks, G.schunks.size())); CHK(dalloc(ctx, &D.qchunk, (size_t)Q + 1));
-  { int lo = 0, hi = 0; (void)hipDeviceGetStreamPriorityRange(&lo, &hi);      // lowest priority: the shuffle only fills gaps
-    HIPCHK(hipStreamCreateWithPriority(&ctx->side, hipStreamNonBlocking, lo)); }
-  for (int i = 0; i < 2; i++) { HIPCHK(hipEventCreateWithFlags(&ctx->ev_sorted[i], hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&ctx->ev_free[i], hipEventDisableTiming)); }
   if (ctx->shuf_inv) {
     const size_t bins = (size_t)P.nkeys * Q, parts = (size_t)shuffle_parts((uint64_t)ctx->N_global, D.nb, ctx->cells_per_block);
     for (int i = 0; i < 4; i++) { CHK(dalloc(ctx, &ctx->posr[i], (size_t)ctx->N_global)); CHK(dalloc(ctx, &ctx->shuf_partcnt[i], bins * parts));

@@ -206,10 +206,7 @@ void l_normalize(const Launch& L, float* Z, int n, int d, int zs);
 void l_normalize_from(const Launch& L, const float* src, float* dst, int n, int d, int zs);
 // objective partials of the current state (reads R)
 void l_head(const Launch& L, const Dev& D);
-void l_sort_blocks(const Launch& L, const Dev& D, bool fused, uint64_t seed, uint64_t round, uint64_t Nglob, uint64_t goff,
-                   uint64_t cells_per_block);
-void l_sort_hist(const Launch& L, const Dev& D, bool fused, uint64_t seed, uint64_t round, uint64_t Nglob, uint64_t goff, uint64_t cells_per_block);
-void l_sort_tail(const Launch& L, const Dev& D);
+void l_sort_blocks(const Launch& L, const Dev& D);      // one round's padded order from host-uploaded block ids (D.blk)
 struct SortPtrs { int* blk; int* blkv; int* counts; int* offs; int* binoff; int* bincnt; int* boff; int* lorder; int* lcombo; int2* lpair; };
 struct SortBatch { SortPtrs p[4]; };
 struct ShufSets { int2* posr[4]; int2* lpair[4]; int* lorder[4]; int* lcombo[4]; int* boff[4]; int* partcnt[4]; int* binbase[4]; int* bincnt[4]; int* binacc[4]; };

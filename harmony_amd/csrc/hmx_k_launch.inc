@@ -114,36 +114,12 @@ TileLaunch l_chain(const Launch& L, const Dev& D, int workgroups) { return launc
 void l_head(const Launch& L, const Dev& D) {
   HMX_DISPATCH_KD(k_head, dim3(stream_grid(L, D.nitems)), lds_bytes_y(D), D);
 }
-// fused = true: D.blk is produced by the histogram kernel from (seed, round); false: the host uploaded D.blk (injected shuffle)
 static SortPtrs sort_ptrs_of(const Dev& D) { return SortPtrs{D.blk, D.blkv, D.counts, D.offs, D.binoff, D.bincnt, D.boff, D.lorder, D.lcombo, D.lpair}; }
 static BlockIdArgs block_id_args(uint64_t seed, uint64_t round, uint64_t Nglob, uint64_t goff, uint64_t cells_per_block) {
   BlockIdArgs A;
   A.fk = make_keys(seed, round, Nglob); A.fk2 = make_keys(seed, round + 1, Nglob); A.Nglob = Nglob; A.goff = goff; A.cpb = cells_per_block;
   A.inv_cpb = 1.0f / (float)cells_per_block;
   return A;
-}
-// the histogram half (block ids from the Feistel bijection + per-chunk counts): depends on nothing but (seed, round)
-void l_sort_hist(const Launch& L, const Dev& D, bool fused, uint64_t seed, uint64_t round, uint64_t Nglob, uint64_t goff, uint64_t cells_per_block) {
-  const int nV = D.nxt ? D.nb * D.nb : D.nb;
-  const size_t lds = (size_t)nV * sizeof(int);
-  BlockIdBatch AB{}; AB.a[0] = block_id_args(seed, round, Nglob, goff, cells_per_block);
-  SortBatch S{}; S.p[0] = sort_ptrs_of(D);
-  if (fused) hipLaunchKernelGGL(k_sort_hist<true>, dim3(D.nchunks), dim3(WAVE), lds, L.stream, D, AB, S);
-  else hipLaunchKernelGGL(k_sort_hist<false>, dim3(D.nchunks), dim3(WAVE), lds, L.stream, D, AB, S);
-}
-// the dependent half: bin offsets from the counts, then the placement (padding slots = -1: written by k_sort_scatter, bin by bin)
-void l_sort_tail(const Launch& L, const Dev& D) {
-  const int nV = D.nxt ? D.nb * D.nb : D.nb;
-  const size_t lds = (size_t)nV * sizeof(int);
-  SortBatch S{}; S.p[0] = sort_ptrs_of(D);
-  hipLaunchKernelGGL(k_sort_binscan, dim3(nV * D.Q), dim3(WAVE), 0, L.stream, D, S);
-  hipLaunchKernelGGL(k_sort_binoff, dim3(1), dim3(1024), 0, L.stream, D, S);
-  hipLaunchKernelGGL(k_sort_scatter, dim3(D.nchunks), dim3(WAVE), lds, L.stream, D, S);
-}
-void l_sort_blocks(const Launch& L, const Dev& D, bool fused, uint64_t seed, uint64_t round, uint64_t Nglob, uint64_t goff,
-                   uint64_t cells_per_block) {
-  l_sort_hist(L, D, fused, seed, round, Nglob, goff, cells_per_block);
-  l_sort_tail(L, D);
 }
 // The shuffles of `nr` consecutive rounds (first: `round`) in ONE set of four launches, blockIdx.y = the round: the four kernels of a
 // sort are latency-bound chains of small dependent steps, so four rounds cost little more than one -- and inside a cluster_cpp call
@@ -158,6 +134,17 @@ void l_sort_batch(const Launch& L, const Dev& D, const SortBatch& S, int nr, uin
   hipLaunchKernelGGL(k_sort_binscan, dim3(nV * D.Q, nr), dim3(WAVE), 0, L.stream, D, S);
   hipLaunchKernelGGL(k_sort_binoff, dim3(nr), dim3(1024), 0, L.stream, D, S);
   hipLaunchKernelGGL(k_sort_scatter, dim3(D.nchunks, nr), dim3(WAVE), lds, L.stream, D, S);
+}
+// the padded order of one round whose D.blk the host uploaded (injected shuffle): per-chunk counts, bin offsets from the counts, then the
+// placement (padding slots = -1: written by k_sort_scatter, bin by bin)
+void l_sort_blocks(const Launch& L, const Dev& D) {
+  const int nV = D.nxt ? D.nb * D.nb : D.nb;
+  const size_t lds = (size_t)nV * sizeof(int);
+  SortBatch S{}; S.p[0] = sort_ptrs_of(D);
+  hipLaunchKernelGGL(k_sort_hist<false>, dim3(D.nchunks), dim3(WAVE), lds, L.stream, D, BlockIdBatch{}, S);
+  hipLaunchKernelGGL(k_sort_binscan, dim3(nV * D.Q), dim3(WAVE), 0, L.stream, D, S);
+  hipLaunchKernelGGL(k_sort_binoff, dim3(1), dim3(1024), 0, L.stream, D, S);
+  hipLaunchKernelGGL(k_sort_scatter, dim3(D.nchunks), dim3(WAVE), lds, L.stream, D, S);
 }
 // the padded orders of rounds round..round + nr - 1 from the inverse of the shuffle (k_shuf_*)
 int shuffle_parts(uint64_t Nglob, int nb, uint64_t cells_per_block) {

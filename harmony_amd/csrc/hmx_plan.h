@@ -29,6 +29,7 @@ struct Switches {
   bool solve_host = false;                               // HMX_MOE_SOLVE=host
   bool stats_atomic = false;                             // HMX_MOE_STATS=atomic
   bool fused_fold_off = false;                           // HMX_FUSED_FOLD=0
+  int fold_impl = 0;                                     // HMX_FOLD_IMPL=split|merged -> 1 | 2: force the two-kernel fold + penalty / k_foldpen of the step loop (tests)
   int chain = -1, chain_pair = -1;                       // HMX_CHAIN / HMX_CHAIN_PAIR: 0 off | 1 forced | -1 (unset, anything else) by the thresholds
   bool chain_wgs_set = false; int chain_wgs = 0;         // HMX_CHAIN_WGS (tests: two ranks sharing one GPU)
   bool chain_max_tpw_set = false; double chain_max_tpw = 0;      // HMX_CHAIN_MAX_TPW (tests: move the threshold between two shards)
@@ -56,6 +57,7 @@ inline Switches read_switches() {
   s.solve_host = is(getenv("HMX_MOE_SOLVE"), "host");
   s.stats_atomic = is(getenv("HMX_MOE_STATS"), "atomic");
   s.fused_fold_off = is(getenv("HMX_FUSED_FOLD"), "0");
+  e = getenv("HMX_FOLD_IMPL"); s.fold_impl = is(e, "split") ? 1 : is(e, "merged") ? 2 : 0;
   s.chain = tri(getenv("HMX_CHAIN"));
   s.chain_pair = tri(getenv("HMX_CHAIN_PAIR"));
   if ((e = getenv("HMX_CHAIN_WGS"))) { s.chain_wgs_set = true; s.chain_wgs = atoi(e); }

@@ -22,7 +22,7 @@ extern "C" {
  * Tuning / fallback selectors (tests and measurements; the defaults are the measured best):
  *   fields "grid", "upd_wps" (before setup), "upd_tpw", "comm_force";
  *   environment, read by hmx_setup: HMX_GRID, HMX_NREP, HMX_UPD_WPS (2|4), HMX_USIG=0 (general-sigma kernels),
- *   HMX_UPD_THREADS, HMX_UPD_MAXBLOCKS, HMX_STATIC_MAXBLOCKS, HMX_UPD_TPW, HMX_FUSED_FOLD=0, HMX_FOLD_IMPL=split,
+ *   HMX_UPD_THREADS, HMX_UPD_MAXBLOCKS, HMX_STATIC_MAXBLOCKS, HMX_UPD_TPW, HMX_FUSED_FOLD=0, HMX_FOLD_IMPL=split|merged,
  *   HMX_OLDSUM_IMPL=gather|stream1, HMX_MOE_IMPL=v1 (first-generation kernels),
  *   HMX_DOT=f32 (tile kernels: fp32-MFMA distance GEMM only; default: the split-bf16 build wherever its LDS image fits -- same
  *   fp32 accuracy);
@@ -40,7 +40,12 @@ extern "C" {
  *   (rounds whose R rows were not stored), "chain_rounds" (rounds run by a persistent chain);
  *   the last k_tile launch of a kind as it ran (plan_tile_launch, harmony_amd/csrc/hmx_plan.h): "launch:head" "launch:lloyd" "launch:seed" "launch:update"
  *   "launch:chain" -- 9 doubles: valid, bf (1: split-bf16 build), nct, mode, wps, usig (the instantiation k_tile<nct, mode, wps, usig>), threads, blocks,
- *   lds (bytes); -1 while the handle has not made a launch of that kind since hmx_setup. */
+ *   lds (bytes); -1 while the handle has not made a launch of that kind since hmx_setup;
+ *   the plan of the last clustering round (plan_round, harmony_amd/csrc/hmx_round.h): "round:last" -- 8 doubles: path (0 persistent chain, 1 fold in the
+ *   update launch's prologue, 2 step loop), merged (step loop: k_foldpen instead of k_fold + k_penalty), chain_tail (the chain closed the round itself),
+ *   carried (old contributions filed by the pass before: no pass over R), write_next (it filed the next round's), r_store (0: its R rows were not
+ *   written), closing form (0 chain tail, 1 wide clear + k_round_tail, 2 k_round_tail alone, 3 reduce + snapshot), exchanges (in-launch inbox exchanges
+ *   it issued); -1 before the first round. */
 
 /* probes of the R-compatible stream (host only, no device needed; used by the CPU tests) */
 void hmx_r_runif(uint32_t seed, int32_t n, double* out);            /* set.seed(seed); runif(n)                      */

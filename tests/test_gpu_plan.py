@@ -72,3 +72,72 @@ def test_live_handle_runs_the_probed_plan(name, monkeypatch):
         runs = t.pop("ran") and kind != ("update" if on_chain else "chain")
         assert got[kind] == (t if runs else None), (name, kind, got[kind], t)
     assert got["head"] and got["seed"] and (got["chain"] if on_chain else got["update"]), (name, got)
+
+
+# ---- the round plan (harmony_amd/csrc/hmx_round.h): what the handle's last round decided is what the CPU probe plans for it ---------------------------
+ROUND_ENVS = {                          # environment, the path it claims: (RoundPlan::path, merged)
+    "chain": ({}, (0, 1)),
+    "fold_in_prologue": ({"HMX_CHAIN": "0"}, (1, 1)),
+    "merged_step_loop": ({"HMX_CHAIN": "0", "HMX_FUSED_FOLD": "0"}, (2, 1)),
+    "two_kernel_step_loop": ({"HMX_CHAIN": "0", "HMX_FOLD_IMPL": "split"}, (2, 0)),
+    "chain_pushed_first_order": ({}, (0, 1)),
+}
+
+
+@pytest.mark.parametrize("name", sorted(ROUND_ENVS))
+def test_live_handle_runs_the_probed_round_plan(name, monkeypatch):
+    """6000 cells, d = 30, 4 levels, K = 40, up to 6 rounds with the carry forced on: hmx_get("round:last") and the handle's counters against the script
+    tests/test_round_cpu.py drives through the probe for the same switches -- init_cluster's head, then the m rounds the call really ran."""
+    from test_round_cpu import LAST_FIELDS, cluster, init_cluster, rounds, run
+    for k in [k for k in os.environ if k.startswith("HMX_")]:
+        monkeypatch.delenv(k)
+    env, (path, merged) = ROUND_ENVS[name]
+    monkeypatch.setenv("HMX_SOLD_CARRY", "1")
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    pushed = name.endswith("pushed_first_order")
+    N, d, K = 6000, 30, 40
+    Z, meta, _ = synth(N, d=d, levels=(4,), seed=7)
+    skw, _ = prepare_setup_args(Z, meta, list(meta), nclust=K, sigma=0.1)
+
+    def fit(max_iter):
+        skw["max_iter_kmeans"] = max_iter
+        h = Harmony(seed=1)
+        h.setup(**skw)
+        if pushed:                      # queued before init_cluster: its head cannot gather, round 0 takes the order
+            h.push_update_order(np.random.default_rng(3).permutation(N))
+        h.init_cluster_cpp()
+        h.cluster_cpp()
+        return h
+
+    h = fit(6)
+    m = int(h._get("kmeans_rounds")[-1])
+    phi_i, _, _, B = skw["Phi"]
+    combos, counts = np.unique(np.asarray(phi_i).reshape(N, 1), axis=0, return_counts=True)
+    p = plan(N, K, d=d, B=int(B), C_=1, Q=len(combos), nb=int(h._scalar("n_blocks")), cells_per_block=int(h._scalar("cells_per_block")), cus=int(h._scalar("chain_wgs")),
+             usig=1, ntitems=int(((counts + 15) // 16).sum()))
+    cfg = dict(B=int(B), K=K, nb=int(h._scalar("n_blocks")), nrep=p["nrep"], fused_ok=p["fused_ok"], chain_ok=p["chain_ok"], chain_pair=p["chain_pair"], carry_ok=p["carry_ok"],
+               shuf_inv=p["shuf_inv"], seed=1, NT4=p["NT4"], NCT=p["NCT"], upd_wps=p["upd_wps"])
+
+    def script(rounds_run, max_iter):
+        return rounds(run(init_cluster(host_order=int(pushed)) + cluster(rounds_run, True, max_iter=max_iter, host_rounds=(0,) if pushed else ()), max_iter_kmeans=max_iter, **cfg))
+
+    want = script(m, 6)
+    live = dict(zip(LAST_FIELDS, (int(v) for v in h._get("round:last"))))
+    counters = {g: int(h._scalar(g)) for g in ("carried_rounds", "rounds_without_R", "chain_rounds", "sold_carry")}
+    print("ROUND", name, {"m": m, "live": live, "counters": counters})
+    assert counters["sold_carry"] == 1 and 5 <= m <= 6, (name, m, counters)
+    assert live == {k: want[-1][k] for k in LAST_FIELDS}, (name, live, want[-1])
+    assert (live["path"], live["merged"]) == (path, merged), (name, live)
+    assert counters["chain_rounds"] == (m if path == 0 else 0), (name, counters)
+    if not pushed:
+        assert counters["carried_rounds"] == m and counters["rounds_without_R"] == min(m - 1, 4), (name, m, counters)
+        return
+    # the pushed order is round 0's: not carried, rows stored (its tiles are keyed by the block alone: it files nothing); round 1 finds nothing filed either
+    assert (want[0]["carried"], want[0]["r_store"], want[1]["carried"]) == (0, 1, 0)
+    assert counters["carried_rounds"] == sum(r["carried"] for r in want) == m - 2, (name, m, counters)
+    assert counters["rounds_without_R"] == sum(1 - r["r_store"] for r in want), (name, m, counters)
+    h1 = fit(1)                         # the same first round as a call's only one: its plan, read back
+    first = dict(zip(LAST_FIELDS, (int(v) for v in h1._get("round:last"))))
+    assert first == {k: script(1, 1)[0][k] for k in LAST_FIELDS} and (first["carried"], first["r_store"]) == (0, 1), (name, first)
+    assert (int(h1._scalar("carried_rounds")), int(h1._scalar("rounds_without_R"))) == (0, 0)

@@ -339,83 +339,12 @@ int hmx_moe_correct_ridge(hmx_ctx* ctx) {  // src/harmony.cpp:345-638
   if (!ctx->R_valid) return fail(ctx, HMX_ERR_STATE, "R is not available: the clustering call that would have stored it did not complete");
   const double t0 = now_ms();
   const Dev& D = ctx->D;
-  const int K = ctx->K, B = ctx->B, d = ctx->d, Q = ctx->Q;
-  const bool seq = ctx->ridge_arith == 1;
   if (ctx->stale_dist && !ctx->head_is_stale) {      // what dist_mat was computed from (:141 / :221): kept for a stand-alone compute_objective
     l_copy(ctx->L, D.Zc, ctx->Zc_head, (size_t)ctx->N * D.zs); KCHK();
-    l_copy(ctx->L, D.Yt, ctx->Yt_head, (size_t)d * K); KCHK();
+    l_copy(ctx->L, D.Yt, ctx->Yt_head, (size_t)ctx->d * ctx->K); KCHK();
     ctx->head_is_stale = true;
   }
-  { PhaseScope pall(ctx, "correct_ridge_loop");
-  { PhaseScope ph(ctx, "ridge_statistics");   // reference timers Phi_Rk + Phi_cov + Z_tmp + Z_intercept + batch_exprod: ONE pass here
-    l_zero4(ctx->L, D.Sq, (size_t)Q * d * K, D.nq, (size_t)Q * K, nullptr, 0, nullptr, 0); KCHK();      // (one launch instead of two memsets)
-    if (seq) CHK(seq_ridge_stats(ctx));
-    else if (D.moe_mfma) { l_moe_stats_mfma(ctx->L, D); KCHK(); } else { l_moe_stats(ctx->L, D); KCHK(); }
-    CHK(allreduce(ctx, D.Sq, (int64_t)Q * d * K, 1));
-    CHK(allreduce(ctx, D.nq, (int64_t)Q * K, 1)); }
-  if (ctx->solve_on_device) {
-    // the whole correction stays on the device: statistics -> K fp64 solves (one workgroup per cluster) -> apply -> Y;
-    // no host synchronisation (a singular system is reported by the next call that waits for the device)
-    SolveArgs A;
-    A.cov = ctx->sv_cov; A.rhs = ctx->sv_rhs; A.Wall = ctx->sv_Wall; A.mrows = ctx->sv_mrows; A.flags = ctx->sv_flags;
-    A.lambda = ctx->lambda_estimation ? nullptr : ctx->sv_lambda; A.cov_bounds = ctx->sv_cov_bounds;
-    A.alpha = ctx->alpha; A.cutoff = ctx->cutoff; A.use_s0 = seq ? 1 : 0; A.err = ctx->D.solve_err;
-    A.Of = ctx->oe_arith ? ctx->Of : nullptr; A.Ef = ctx->oe_arith ? ctx->Ef : nullptr; A.solve_f32 = ctx->solve_arith;
-    A.ref_tot = (seq && ctx->C > 1) ? ctx->rg_tot : nullptr; A.pair_tot = ctx->rp_tot; A.pair_idx = ctx->pair_idx;
-    { PhaseScope ph(ctx, "arma_inv"); l_moe_solve(ctx->L, D, A); KCHK(); }
-    { PhaseScope ph(ctx, "update_Zcorr");
-      if (D.moe_mfma) { l_moe_apply_mfma(ctx->L, D); KCHK(); } else { l_moe_apply(ctx->L, D); KCHK(); } }
-    ctx->y_on_device = true; ctx->solve_pending = true;
-    ctx->timers["moe_correct_ridge"] += now_ms() - t0;
-    return 0;
-  }
-  }
-  std::vector<double> Sq((size_t)Q * d * K), nq((size_t)Q * K);
-  std::vector<long long> ofx((size_t)B * K);
-  CHK(d2h(ctx, Sq.data(), D.Sq, Sq.size())); CHK(d2h(ctx, nq.data(), D.nq, nq.size())); CHK(d2h(ctx, ofx.data(), D.O_fx, ofx.size()));
-  std::vector<double> S0, n0;
-  if (seq) { S0.resize((size_t)K * d); n0.resize((size_t)K); CHK(d2h(ctx, S0.data(), D.S0, S0.size())); CHK(d2h(ctx, n0.data(), D.n0, n0.size())); }
-  const double t1 = now_ms();
-  const std::vector<float> O = table_O(ctx, ofx), E = table_E(ctx, ofx);
-  CHK(sync_solve_results(ctx));        // (host solve path: the centroids may still live on the device only)
-  std::vector<float> Wq((size_t)Q * K * d), Ynew = ctx->Y;
-  std::vector<SolveOut> outs(K);
-  {
-    unsigned nt = std::thread::hardware_concurrency(); if (nt < 1) nt = 1; if (nt > 16) nt = 16; if ((int)nt > K) nt = K;
-    if ((size_t)K * (B + 1) * (B + 1) < 200000) nt = 1;
-    std::vector<std::thread> th;
-    auto work = [&](int t) { for (int k = t; k < K; k += (int)nt) solve_cluster(ctx, k, O, E, Sq, nq, Wq, Ynew, outs[k], seq ? &S0[(size_t)k * d] : nullptr, seq ? &n0[k] : nullptr); };
-    if (nt == 1) work(0);
-    else { for (unsigned t = 0; t < nt; t++) th.emplace_back(work, (int)t); for (auto& x : th) x.join(); }
-  }
-  ctx->subset_clusters = ctx->skipped_clusters = 0;
-  for (int k = 0; k < K; k++) {
-    if (outs[k].status) return fail(ctx, outs[k].status, "singular ridge system");
-    if (outs[k].subset) ctx->subset_clusters++;
-    if (outs[k].skipped) ctx->skipped_clusters++;
-    else { ctx->W = outs[k].W; ctx->W_rows = outs[k].m; }
-  }
-  ctx->timers["moe_solve_host"] += now_ms() - t1;
-  if (D.moe_mfma) {
-    // image[q][qd][s][p][c][i] = Wq[q][cluster(s,p)][16*(4qd+i)+c], cluster(s,p) as tile_dots assigns reduction slots
-    std::vector<float> img((size_t)Q * D.wNQ * D.wNS * 256, 0.f);
-    for (int q = 0; q < Q; q++) for (int qd = 0; qd < D.wNQ; qd++) for (int s = 0; s < D.wNS; s++) for (int p = 0; p < 4; p++) {
-      const int k = (s < 4 * D.wNT4) ? 16 * (s / 4) + 4 * p + (s % 4) : 16 * D.wNT4 + 4 * (s - 4 * D.wNT4) + p;
-      if (k >= K) continue;
-      const float* w = &Wq[((size_t)q * K + k) * d];
-      float* o = &img[((((size_t)q * D.wNQ + qd) * D.wNS + s) * 4 + p) * 64];
-      for (int c = 0; c < 16; c++) for (int i = 0; i < 4; i++) { const int jj = 16 * (4 * qd + i) + c; if (jj < d) o[c * 4 + i] = w[jj]; }
-    }
-    CHK(h2d(ctx, D.Wimg, img.data(), img.size()));
-    l_moe_apply_mfma(ctx->L, D); KCHK();   // Z_corr = Z_orig - sum_k R_k W_k[levels]   :347,:615
-  } else {
-    CHK(h2d(ctx, D.Wq, Wq.data(), Wq.size()));
-    l_moe_apply(ctx->L, D); KCHK();
-  }
-  ctx->Y = Ynew;
-  normalise_cols(ctx->Y, d, K);     // :633
-  CHK(upload_Y(ctx));
-  HIPCHK(hipStreamSynchronize(ctx->L.stream));
+  CHK(moe_correct_ridge(ctx));      // hmx_api_ridge.inc
   ctx->timers["moe_correct_ridge"] += now_ms() - t0;
   return 0;
 }

@@ -178,6 +178,12 @@ int64_t hmx_get(hmx_ctx* ctx, const char* field, double* out, int64_t cap) {
       const TileLaunch& t = ctx->last_tile[k];
       return vec(std::vector<double>{(double)t.valid, (double)t.bf, (double)t.nct, (double)t.mode, (double)t.wps, (double)t.usig, (double)t.threads, (double)t.blocks, (double)t.lds});
     }
+    // ... and of the ridge correction (plan_ridge_launch): valid, mfma, p0, p1, grid x, y, z, threads, lds, the solve's lds_b_bytes, lds_body_bytes, lds_mask_off, the reduce launch's grid x, y
+    for (int k = 0; k < 3; k++) if (f.substr(7) == RIDGE_KIND_NAME[k] && ctx->ridge_seen[k]) {
+      const RidgeLaunch& t = ctx->last_ridge[k];
+      return vec(std::vector<double>{(double)t.valid, (double)t.mfma, (double)t.p0, (double)t.p1, (double)t.gx, (double)t.gy, (double)t.gz, (double)t.threads, (double)t.lds,
+                                     (double)t.lds_b_bytes, (double)t.lds_body_bytes, (double)t.lds_mask_off, (double)t.rgx, (double)t.rgy});
+    }
     return -1;      // (no such kind, or no launch of it on this handle yet)
   }
   if (f == "round:last") {      // the plan of the last round of update_R (hmx_round.h): path, merged, chain_tail, carried, write_next, r_store, closing form, exchanges

@@ -1,4 +1,4 @@
-// hmx_api_ridge.inc -- part of hmx_api.cpp (included there, ONE translation unit): ridge solves on the host (HMX_MOE_SOLVE=host) and moe_correct_ridge's orchestration
+// hmx_api_ridge.inc -- part of hmx_api.cpp (included there, ONE translation unit): ridge solves on the host (HMX_MOE_SOLVE=host) and moe_correct_ridge's orchestration (at the end)
 // ---- ridge solves (src/harmony.cpp:358-611), fp64, one cluster at a time --------------------------
 bool chol_solve(std::vector<double>& A, int n, std::vector<double>& Bm, int m) {  // column-major, in place
   for (int c = 0; c < n; c++) {
@@ -157,4 +157,89 @@ std::vector<float> table_E(const hmx_ctx* ctx, const std::vector<long long>& ofx
     for (int b = 0; b < B; b++) E[(size_t)b * K + k] = (float)(rsd * (double)ctx->Pr_b[b]);
   }
   return E;
+}
+
+// ---- moe_correct_ridge (src/harmony.cpp:345-638): statistics, then the device tail or the host tail ------------------------------------------------
+// a launch of the correction as its launcher returned it: kept for hmx_get("launch:stats" | "launch:solve" | "launch:apply"); one that could not be made is a limit of the shape
+int ridge_ran(hmx_ctx* ctx, RidgeKind kind, const RidgeLaunch& t) {
+  ctx->last_ridge[(int)kind] = t; ctx->ridge_seen[(int)kind] = true;
+  return t.valid ? 0 : fail(ctx, HMX_ERR_LIMIT, std::string("no ridge launch for kind ") + RIDGE_KIND_NAME[(int)kind] + ": " + (t.mfma ? "MFMA" : "first-generation") + " form, parameters " +
+                                                    std::to_string(t.p0) + ", " + std::to_string(t.p1) + ", " + std::to_string(t.lds) + " bytes of LDS (over the limit, or no such instantiation)");
+}
+// reference timers Phi_Rk + Phi_cov + Z_tmp + Z_intercept + batch_exprod: ONE pass here (the reference's sequential sums / the slot form / the first generation), all-reduced
+int ridge_statistics(hmx_ctx* ctx) {
+  const Dev& D = ctx->D;
+  PhaseScope ph(ctx, "ridge_statistics");
+  l_zero4(ctx->L, D.Sq, (size_t)D.Q * D.d * D.K, D.nq, (size_t)D.Q * D.K, nullptr, 0, nullptr, 0); KCHK();      // (one launch instead of two memsets)
+  if (ctx->ridge_arith == 1) CHK(seq_ridge_stats(ctx));
+  else { CHK(ridge_ran(ctx, RidgeKind::Stats, l_moe_stats(ctx->L, D))); KCHK(); }
+  CHK(allreduce(ctx, D.Sq, (int64_t)D.Q * D.d * D.K, 1));
+  return allreduce(ctx, D.nq, (int64_t)D.Q * D.K, 1);
+}
+// the whole correction stays on the device: statistics -> K fp64 solves (one workgroup per cluster) -> apply -> Y;
+// no host synchronisation (a singular system is reported by the next call that waits for the device)
+int ridge_device_tail(hmx_ctx* ctx) {
+  const Dev& D = ctx->D;
+  const bool seq = ctx->ridge_arith == 1;
+  const RidgeLaunch s = plan_ridge_launch(ridge_geom(D, ctx->L), RidgeKind::Solve);
+  SolveArgs A;
+  A.cov = ctx->sv_cov; A.rhs = ctx->sv_rhs; A.Wall = ctx->sv_Wall; A.mrows = ctx->sv_mrows; A.flags = ctx->sv_flags;
+  A.lambda = ctx->lambda_estimation ? nullptr : ctx->sv_lambda; A.cov_bounds = ctx->sv_cov_bounds;
+  A.alpha = ctx->alpha; A.cutoff = ctx->cutoff; A.use_s0 = seq ? 1 : 0; A.err = ctx->D.solve_err;
+  A.Of = ctx->oe_arith ? ctx->Of : nullptr; A.Ef = ctx->oe_arith ? ctx->Ef : nullptr; A.solve_f32 = ctx->solve_arith;
+  A.ref_tot = (seq && ctx->C > 1) ? ctx->rg_tot : nullptr; A.pair_tot = ctx->rp_tot; A.pair_idx = ctx->pair_idx;
+  A.lds_b_bytes = s.lds_b_bytes; A.lds_body_bytes = s.lds_body_bytes; A.lds_mask_off = s.lds_mask_off;
+  { PhaseScope ph(ctx, "arma_inv"); CHK(ridge_ran(ctx, RidgeKind::Solve, l_moe_solve(ctx->L, D, A))); KCHK(); }
+  { PhaseScope ph(ctx, "update_Zcorr"); CHK(ridge_ran(ctx, RidgeKind::Apply, l_moe_apply(ctx->L, D))); KCHK(); }
+  ctx->y_on_device = true; ctx->solve_pending = true;
+  return 0;
+}
+// HMX_MOE_SOLVE=host, or more levels than the device solve's LDS takes: statistics to the host, K threaded fp64 solves, table (or its MFMA image) and centroids back
+int ridge_host_tail(hmx_ctx* ctx) {
+  const Dev& D = ctx->D;
+  const int K = ctx->K, B = ctx->B, d = ctx->d, Q = ctx->Q;
+  const bool seq = ctx->ridge_arith == 1;
+  std::vector<double> Sq((size_t)Q * d * K), nq((size_t)Q * K);
+  std::vector<long long> ofx((size_t)B * K);
+  CHK(d2h(ctx, Sq.data(), D.Sq, Sq.size())); CHK(d2h(ctx, nq.data(), D.nq, nq.size())); CHK(d2h(ctx, ofx.data(), D.O_fx, ofx.size()));
+  std::vector<double> S0, n0;
+  if (seq) { S0.resize((size_t)K * d); n0.resize((size_t)K); CHK(d2h(ctx, S0.data(), D.S0, S0.size())); CHK(d2h(ctx, n0.data(), D.n0, n0.size())); }
+  const double t1 = now_ms();
+  const std::vector<float> O = table_O(ctx, ofx), E = table_E(ctx, ofx);
+  CHK(sync_solve_results(ctx));        // (host solve path: the centroids may still live on the device only)
+  std::vector<float> Wq((size_t)Q * K * d), Ynew = ctx->Y;
+  std::vector<SolveOut> outs(K);
+  {
+    unsigned nt = std::thread::hardware_concurrency(); if (nt < 1) nt = 1; if (nt > 16) nt = 16; if ((int)nt > K) nt = K;
+    if ((size_t)K * (B + 1) * (B + 1) < 200000) nt = 1;
+    std::vector<std::thread> th;
+    auto work = [&](int t) { for (int k = t; k < K; k += (int)nt) solve_cluster(ctx, k, O, E, Sq, nq, Wq, Ynew, outs[k], seq ? &S0[(size_t)k * d] : nullptr, seq ? &n0[k] : nullptr); };
+    if (nt == 1) work(0);
+    else { for (unsigned t = 0; t < nt; t++) th.emplace_back(work, (int)t); for (auto& x : th) x.join(); }
+  }
+  ctx->subset_clusters = ctx->skipped_clusters = 0;
+  for (int k = 0; k < K; k++) {
+    if (outs[k].status) return fail(ctx, outs[k].status, "singular ridge system");
+    if (outs[k].subset) ctx->subset_clusters++;
+    if (outs[k].skipped) ctx->skipped_clusters++;
+    else { ctx->W = outs[k].W; ctx->W_rows = outs[k].m; }
+  }
+  ctx->timers["moe_solve_host"] += now_ms() - t1;
+  if (D.moe_mfma) {      // the table as k_moe_apply_mfma's B-operand image (entries of clusters and PCs beyond K, d stay 0)
+    std::vector<float> img((size_t)Q * D.wNQ * D.wNS * 256, 0.f);
+    for (int q = 0; q < Q; q++) for (int k = 0; k < K; k++) for (int j = 0; j < d; j++) img[wimg_index(D, q, k, j)] = Wq[((size_t)q * K + k) * d + j];
+    CHK(h2d(ctx, D.Wimg, img.data(), img.size()));
+  } else CHK(h2d(ctx, D.Wq, Wq.data(), Wq.size()));
+  CHK(ridge_ran(ctx, RidgeKind::Apply, l_moe_apply(ctx->L, D))); KCHK();   // Z_corr = Z_orig - sum_k R_k W_k[levels]   :347,:615
+  ctx->Y = Ynew;
+  normalise_cols(ctx->Y, d, K);     // :633
+  CHK(upload_Y(ctx));
+  HIPCHK(hipStreamSynchronize(ctx->L.stream));
+  return 0;
+}
+int moe_correct_ridge(hmx_ctx* ctx) {
+  { PhaseScope pall(ctx, "correct_ridge_loop");
+    CHK(ridge_statistics(ctx));
+    if (ctx->solve_on_device) return ridge_device_tail(ctx); }
+  return ridge_host_tail(ctx);
 }

@@ -232,6 +232,7 @@ struct hmx_ctx {
   bool R_valid = false, r_store_always = false;
   int64_t rounds_without_R = 0;
   TileLaunch last_tile[5]; bool tile_seen[5] = {};      // the last k_tile launch of every TileKind, as it ran (hmx_get "launch:<kind>")
+  RidgeLaunch last_ridge[3]; bool ridge_seen[3] = {};   // the last launch of every RidgeKind, as it ran (hmx_get "launch:stats" | "launch:solve" | "launch:apply")
   int64_t carried_rounds = 0;
   bool chain_ok = false; int chain_wgs = 0; uint64_t chain_rounds = 0;   // persistent block chain (one launch per round)
   int tun_tpw = -1, tun_wps = -1;  // tunables set through hmx_set_int before setup

@@ -151,8 +151,8 @@ struct Dev {
   double* Sq;       // [Q][K][d]  sum_i R_ki z_ij over cells of combination q
   double* nq;       // [Q][K]     sum_i R_ki
   // deterministic statistics pass (k_moe_stats_q): per-(workgroup, combination run) partial slots, reduced in fixed order
-  int st_dma, st_nwg, st_cpw;       // enabled, workgroups, 16-cell tiles per workgroup
-  int st_halves, st_KH;             // 2: K in (128, 224] -- the pass runs once per half of the clusters ([0, st_KH) / [st_KH, K), blockIdx.y), each with <= 8 cluster tiles
+  int st_dma, st_nwg, st_cpw;       // enabled (= moe_mfma), workgroups, 16-cell tiles per workgroup
+  int st_halves, st_KH;             // 2: K in (128, 256] -- the pass runs once per half of the clusters ([0, st_KH) / [st_KH, K), blockIdx.y), each with <= 8 cluster tiles
   double* st_part;                  // [slots][K*d + K]
   int* st_slot0;                    // [st_nwg] first slot of every workgroup
   int* st_qptr; int* st_qslots;     // CSR: slots of every combination in ascending (= cell) order
@@ -163,7 +163,7 @@ struct Dev {
   float* Wq;        // [Q][K][d]  correction table
   float* Wimg;      // [Q][wNQ][wNS][4][16][4] the same table as MFMA B-operand image (clusters = reduction dim)
   int wNQ, wNT4, wtail, wNS;  // image geometry for k_moe_apply_mfma (valid when moe_mfma)
-  int moe_mfma;     // 1: MFMA stats/apply kernels (needs K % 4 == 0, d <= 64, K <= 128)
+  int moe_mfma;     // 1: MFMA stats/apply kernels (needs K % 4 == 0, d <= 64, K <= 256)
   // kmeans init
   long long* km_gcells; double* km_rows; unsigned* km_excl;   // [K] chosen global cells, [K][d] their rows, [K] exclusion list
   unsigned long long* seedmin;  // [K] packed (key bits << 32 | global cell)
@@ -279,6 +279,15 @@ __host__ __device__ inline void bfimg_store_all(const Dev& D, int j, int k, floa
     bfimg_store(D.Yimg3p + (size_t)h * nctp * D.NS2 * 3 * 512, nctp, D.NS2, j, h ? k - D.KH : k, y);
   }
 }
+// float index of (combination q, cluster k, PC j) in the correction table's MFMA B-operand image, Dev::Wimg [Q][wNQ][wNS][4][16][4]: the clusters are the reduction
+// dim -- cluster k sits in reduction step s, slot p as tile_dots assigns them -- and PC j is column j & 15, component (j & 63) >> 4 of quad j >> 6
+__host__ __device__ inline size_t wimg_index(const Dev& D, int q, int k, int j) {
+  int s, p;
+  if (k < 16 * D.wNT4) { const int t = k >> 4, r = k & 15; p = r >> 2; s = 4 * t + (r & 3); }
+  else { const int r = k - 16 * D.wNT4; s = 4 * D.wNT4 + (r >> 2); p = r & 3; }
+  const int qd = j >> 6, ii = (j & 63) >> 4, cc = j & 15;
+  return ((((size_t)q * D.wNQ + qd) * D.wNS + s) * 4 + p) * 64 + cc * 4 + ii;
+}
 constexpr int P2P_CAP = 65536;                       // K x B entries an inbox holds per (plane, source): 200 clusters x 200 levels (BASELINE configs[4]) fit
 // an inbox = [4 planes][8 sources][P2P_CAP entries][2 granules]: planes 0 / 1 = the block chain's exchanges (alternating by exchange
 // number), planes 2 / 3 = the generic small all-reduces (alternating by call number); 64 granules behind them: the connection self-test
@@ -292,11 +301,13 @@ void l_p2p_allreduce(const Launch& L, const Dev& D, void* buf, int n, int dtype,
 void l_p2p_allreduce_big(const Launch& L, const Dev& D, void* buf, int n, int dtype, unsigned seq, int* err);
 void l_p2p_selftest(const Launch& L, const Dev& D, unsigned tag, int* result);   // the whole block chain of a round: one persistent launch
 void l_objective_tables(const Launch& L, const Dev& D);  // cross-entropy term only -> obj[4]
-void l_moe_stats(const Launch& L, const Dev& D);
-void l_moe_apply(const Launch& L, const Dev& D);
-void l_moe_stats_mfma(const Launch& L, const Dev& D);
-void l_moe_solve(const Launch& L, const Dev& D, const SolveArgs& A);
-void l_moe_apply_mfma(const Launch& L, const Dev& D);
+// the ridge correction's launches (statistics + their slot reduction, device solve, apply), planned by plan_ridge_launch (hmx_plan.h) from ridge_geom's fields; returned: the
+// launch as it ran -- valid = false: none, the caller reports HMX_ERR_LIMIT.  l_moe_solve: A's lds_* values are the plan's (the host fills them from the same plan)
+struct RidgeGeom; struct RidgeLaunch;
+RidgeGeom ridge_geom(const Dev& D, const Launch& L);
+RidgeLaunch l_moe_stats(const Launch& L, const Dev& D);
+RidgeLaunch l_moe_solve(const Launch& L, const Dev& D, const SolveArgs& A);
+RidgeLaunch l_moe_apply(const Launch& L, const Dev& D);
 void l_seed_race_u(const Launch& L, const Dev& D, const float* u, int a0, int na, int only, uint64_t goff, const unsigned* excl,
                    int nexcl);
 void l_gather_rows(const Launch& L, const Dev& D, const long long* gcells, uint64_t goff, double* rows);

@@ -759,7 +759,7 @@ __global__ __launch_bounds__(1024) void k_moe_solve(Dev D, SolveArgs A) {
       D.Wq[((size_t)q * K + k) * d + j] = w;
     }
   }
-  if (D.moe_mfma) {   // MFMA B-operand image of the correction table (clusters = reduction dim), as the host builder lays it out
+  if (D.moe_mfma) {   // MFMA B-operand image of the correction table (clusters = reduction dim), wimg_index(D, q, k, j) with the cluster's step and slot hoisted
     int s_, p_;
     if (k < 16 * D.wNT4) { const int t = k >> 4, r = k & 15; p_ = r >> 2; s_ = 4 * t + (r & 3); }
     else { const int r = k - 16 * D.wNT4; s_ = 4 * D.wNT4 + (r >> 2); p_ = r & 3; }
@@ -784,99 +784,10 @@ __global__ __launch_bounds__(1024) void k_moe_solve(Dev D, SolveArgs A) {
 }
 
 // ---- MFMA variants of the two MoE passes (static 16-cell tiles, rows of a tile are contiguous in HBM) ----
-// k_moe_stats_mfma: Sq[q] (K x d) += R_tile^T (K x 16) * Zo_tile (16 x d): the 16 cells are the MFMA reduction dim.
-//   A[i = cluster 16ct+(l&15)][slot l>>4] = R[cell 4s+(l>>4)][cluster],  B[slot][j = PC 16pt+(l&15)] = Zo[cell][PC]
-//   D: lane l holds clusters 16ct+4(l>>4)+reg x PC 16pt+(l&15); accumulated over a run of tiles, flushed with fp64 atomics.
-// Work split: a workgroup streams a contiguous range of tiles; its wave w owns PC tile w (blockDim = 64*ceil(d/16)),
-// so a wave carries only NCT fp32 MFMA accumulators (folded into fp64 shadows every 4 tiles = 64 cells) and the
-// K x d result of a run is flushed ONCE per workgroup, not once per wave (the fp64 atomics dominated otherwise).
-// CTS > 1 (K > 128): the cluster tiles are split over CTS workgroups per tile range (blockIdx % CTS = cluster-tile group),
-// each wave carrying NCTT / CTS accumulators + fp64 shadows.  (For K <= 128 the split was measured SLOWER -- 597 vs 355 us: the
-// operand loads, not the registers, limit this kernel -- so it is only used where one wave cannot hold all cluster tiles.)
-// (launch bounds 256 = one wave per SIMD with the whole 512-entry register file: with a 256-register budget hipcc serialises
-//  the 32 operand loads of a tile with a wait after each, 355 -> 800 us -- hence the split across workgroups, not waves)
-template <int NCTT, int CTS>
-__global__ __launch_bounds__(256) void k_moe_stats_mfma(Dev D, int tiles_per_wg, int npt) {
-  constexpr int NCT = (NCTT + CTS - 1) / CTS;   // cluster tiles of this wave
-  const int lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
-  const int pt = threadIdx.x >> 6, grp = (CTS > 1) ? (int)(blockIdx.x % CTS) : 0, ct0 = grp * NCT;   // first cluster tile of this workgroup
-  const int K = D.K, d = D.d, zs = D.zs;
-  const int ts = (int)(blockIdx.x / CTS) * tiles_per_wg, te = min(D.ntitems, ts + tiles_per_wg);
-  if (ts >= te) return;
-  const int jj = 16 * pt + c;           // this lane's PC
-  const bool jv = jj < d;
-  f32x4 acc[NCT];
-  double sh[NCT][4], nsh[NCT];
-  float nacc[NCT];
-#pragma unroll
-  for (int ct = 0; ct < NCT; ct++) {
-    acc[ct] = f32x4{0.f, 0.f, 0.f, 0.f}; nacc[ct] = 0.0f; nsh[ct] = 0.0;
-#pragma unroll
-    for (int reg = 0; reg < 4; reg++) sh[ct][reg] = 0.0;
-  }
-  auto fold = [&]() {
-#pragma unroll
-    for (int ct = 0; ct < NCT; ct++) {
-#pragma unroll
-      for (int reg = 0; reg < 4; reg++) sh[ct][reg] += (double)acc[ct][reg];
-      acc[ct] = f32x4{0.f, 0.f, 0.f, 0.f};
-      nsh[ct] += (double)nacc[ct]; nacc[ct] = 0.0f;
-    }
-  };
-  auto flush = [&](int q) {
-    double* S = D.Sq + (size_t)q * d * K;
-#pragma unroll
-    for (int ct = 0; ct < NCT; ct++) {
-#pragma unroll
-      for (int reg = 0; reg < 4; reg++) {
-        const int k = 16 * (ct0 + ct) + 4 * g + reg;
-        if (jv && k < K && sh[ct][reg] != 0.0) atomicAdd(&S[(size_t)k * d + jj], sh[ct][reg]);
-        sh[ct][reg] = 0.0;
-      }
-      if (pt == 0) {                            // sum_i R_ki of cluster 16ct+c: add the four cell slots
-        double v = nsh[ct];
-        v += __shfl_xor(v, 16, 64); v += __shfl_xor(v, 32, 64);
-        if (g == 0 && 16 * (ct0 + ct) + c < K) atomicAdd(&D.nq[(size_t)q * K + 16 * (ct0 + ct) + c], v);
-      }
-      nsh[ct] = 0.0;
-    }
-  };
-  // tile descriptors one tile ahead and as per-lane loads (a uniform load becomes load + readfirstlane + vmcnt(0): one more
-  // serial memory latency per tile in front of the operand loads)
-  auto item_at = [&](int tile) -> Item {
-    const Item* tp = D.titems + min(tile, te - 1);
-    asm volatile("" : "+v"(tp));
-    return *tp;
-  };
-  Item itN = item_at(ts);
-  int curq = __builtin_amdgcn_readfirstlane(itN.q);
-  for (int tile = ts; tile < te; ++tile) {
-    const Item it = itN;
-    itN = item_at(tile + 1);
-    const int tq = __builtin_amdgcn_readfirstlane(it.q);
-    if (tq != curq) { fold(); flush(curq); curq = tq; }
-    const size_t c0 = (size_t)it.start;
-#pragma unroll
-    for (int st = 0; st < 4; ++st) {
-      const int cell = 4 * st + g;                       // cell slot of this lane in this step
-      const bool cv = cell < it.cnt;
-      const size_t row = c0 + (cv ? cell : 0);
-      float a[NCT];
-#pragma unroll
-      for (int ct = 0; ct < NCT; ct++) a[ct] = ld_or(D.R, row * K + min(16 * (ct0 + ct) + c, K - 1), cv && 16 * (ct0 + ct) + c < K, 0.0f);
-      const float b = ld_or(D.Zo, row * zs + min(jj, zs - 1), cv && jv, 0.0f);
-#pragma unroll
-      for (int ct = 0; ct < NCT; ct++) {
-        nacc[ct] += a[ct];
-        acc[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[ct], b, acc[ct], 0, 0, 0);
-      }
-    }
-    if (((tile - ts) & 3) == 3) fold();
-  }
-  fold(); flush(curq);
-}
-
-// k_moe_stats_q: k_moe_stats_mfma with (a) 16-byte operand loads and (b) a bit-reproducible reduction (K <= 128).
+// k_moe_stats_q: Sq[q] (K x d) += R_tile^T (K x 16) * Zo_tile (16 x d): the 16 cells are the MFMA reduction dim.  A workgroup streams a contiguous range of tiles; its
+// wave w owns PC tile w (blockDim = 64 * PC tiles, the ones column at index d included), so a wave carries only NCT fp32 MFMA accumulators, folded into fp64 shadows every
+// 4 tiles = 64 cells, and the K x (d + 1) result of a combination run is written ONCE per workgroup, not once per wave.  Against the first MFMA form (dword operand gathers,
+// fp64 atomics into Sq; retired, docs/history.md) it has (a) 16-byte operand loads and (b) a bit-reproducible reduction.
 //  (a) Which cluster an MFMA row stands for is free: inside a quad of cluster tiles (64 clusters) row m of tile i stands for
 //      cluster 64 qd + nt m + i (nt = tiles of the quad: 4, or what is left in the last quad), so the nt A operands a lane
 //      needs for one cell are CONSECUTIVE floats of its R row -- one dwordx4 (x3 / x2 / x1) load instead of nt dword gathers:

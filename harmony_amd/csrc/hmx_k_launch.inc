@@ -247,88 +247,49 @@ bool l_obj_terms_mfma(const Launch& L, const Dev& D, const float* M, float* T, l
 #undef HMX_OT
   return true;
 }
-void l_moe_stats(const Launch& L, const Dev& D) {
-  const int zch = (D.d + 31) / 32;
-  int dp = (D.d + zch - 1) / zch;
-  dp = (dp + 3) / 4 * 4;
-  const dim3 grid(stream_grid(L, D.nitems), (D.K + 127) / 128, (D.d + dp - 1) / dp);
-  switch (dp) {
-    case 4: hipLaunchKernelGGL(k_moe_stats<4>, grid, dim3(TPB), 0, L.stream, D); break;
-    case 8: hipLaunchKernelGGL(k_moe_stats<8>, grid, dim3(TPB), 0, L.stream, D); break;
-    case 12: hipLaunchKernelGGL(k_moe_stats<12>, grid, dim3(TPB), 0, L.stream, D); break;
-    case 16: hipLaunchKernelGGL(k_moe_stats<16>, grid, dim3(TPB), 0, L.stream, D); break;
-    case 20: hipLaunchKernelGGL(k_moe_stats<20>, grid, dim3(TPB), 0, L.stream, D); break;
-    case 24: hipLaunchKernelGGL(k_moe_stats<24>, grid, dim3(TPB), 0, L.stream, D); break;
-    case 28: hipLaunchKernelGGL(k_moe_stats<28>, grid, dim3(TPB), 0, L.stream, D); break;
-    default: hipLaunchKernelGGL(k_moe_stats<32>, grid, dim3(TPB), 0, L.stream, D); break;
-  }
+// ---- the ridge correction's launches: hmx_plan.h plans them (plan_ridge_launch), the launchers map the plan to an instantiation.  Every instantiation of a family, once:
+#define HMX_RIDGE_STATS_TUPLES(X) X(4) X(8) X(12) X(16) X(20) X(24) X(28) X(32)                                                       /* k_moe_stats<DP> */
+#define HMX_RIDGE_STATS_Q_TUPLES(X) X(1, false) X(2, false) X(3, false) X(4, false) X(5, false) X(6, false) X(7, false) X(8, false)   /* k_moe_stats_q<NCT, SHL> */ \
+                                  X(1, true) X(2, true) X(3, true) X(4, true) X(5, true) X(6, true) X(7, true) X(8, true)
+#define HMX_RIDGE_APPLY_TUPLES(X) X(1, 1) X(2, 1) X(3, 1) X(4, 1) X(1, 2) X(2, 2) X(3, 2) X(4, 2)                                       /* k_moe_apply<KPL, DPL> */
+#define HMX_RIDGE_APPLY_MFMA_TUPLES(X) X(1) X(2) X(3) X(4)                                                                             /* k_moe_apply_mfma<NPT> */
+RidgeGeom ridge_geom(const Dev& D, const Launch& L) {
+  RidgeGeom g;
+  g.K = D.K; g.KP = D.KP; g.d = D.d; g.B = D.B; g.C = D.C; g.Q = D.Q; g.NCT = D.NCT; g.moe_mfma = D.moe_mfma; g.st_dma = D.st_dma; g.st_halves = D.st_halves; g.st_KH = D.st_KH;
+  g.st_nwg = D.st_nwg; g.wNQ = D.wNQ; g.wNS = D.wNS; g.nitems = D.nitems; g.naitems = D.naitems; g.grid = L.grid;
+  return g;
 }
-void l_moe_apply(const Launch& L, const Dev& D) {
-  const int dpl = D.d > 64 ? 2 : 1;
-  const size_t lds = (size_t)D.K * 64 * dpl * sizeof(float);
-  int g = D.naitems < 4 * L.grid ? D.naitems : 4 * L.grid;
-  if (g < 1) g = 1;
-  const dim3 grid(g);
-  HMX_DISPATCH_KD(k_moe_apply, grid, lds, D);
+// The three launchers: plan, dispatch, return the launch as it ran; valid = false: nothing was launched (LDS over the limit, no such instantiation) -- the caller reports it.
+#define HMX_RIDGE_LAUNCH(KERNEL, ...) hipLaunchKernelGGL(KERNEL, dim3((unsigned)t.gx, (unsigned)t.gy, (unsigned)t.gz), dim3((unsigned)t.threads), t.lds, L.stream, __VA_ARGS__)
+RidgeLaunch l_moe_stats(const Launch& L, const Dev& D) {
+  RidgeLaunch t = plan_ridge_launch(ridge_geom(D, L), RidgeKind::Stats);
+  if (!t.valid) return t;
+#define HMX_MS_CASE(DP) case DP: HMX_RIDGE_LAUNCH(k_moe_stats<DP>, D); return t;
+#define HMX_MSQ_CASE(N, SHL) case 2 * N + (SHL ? 1 : 0): HMX_RIDGE_LAUNCH((k_moe_stats_q<N, SHL>), D, D.st_cpw); break;
+  if (!t.mfma) switch (t.p0) { HMX_RIDGE_STATS_TUPLES(HMX_MS_CASE) default: t.valid = false; return t; }
+  switch (2 * t.p0 + t.p1) { HMX_RIDGE_STATS_Q_TUPLES(HMX_MSQ_CASE) default: t.valid = false; return t; }
+#undef HMX_MS_CASE
+#undef HMX_MSQ_CASE
+  hipLaunchKernelGGL(k_moe_stats_reduce, dim3((unsigned)t.rgx, (unsigned)t.rgy), dim3(256), 0, L.stream, D);      // the slots of every combination, in ascending order
+  return t;
 }
-void l_moe_solve(const Launch& L, const Dev& D, const SolveArgs& A0) {
-  SolveArgs A = A0;
-  const size_t M = (size_t)D.B + 1;
-  const size_t ints = (((size_t)4 * D.B + 6 + D.C) & ~(size_t)1) * sizeof(int);
-  const size_t panel = M * 16 * sizeof(double), ball = M * D.d * sizeof(double);
-  size_t body = panel;
-  if (ints + ball <= LDS_BUDGET) body = std::max(panel, ball);     // the d right-hand sides live in LDS during the substitution
-  if (ints + body > 158 * 1024) body = 0;                           // (B + 1 > ~1200 levels: outside the device-solve envelope, see hmx_setup)
-  A.lds_b_bytes = (body >= ball) ? ball : 0;
-  A.lds_body_bytes = body;
-  // coupling masks of the Schur complement: one bit per (row, eliminated level) -- only while they are small
-  const size_t maskb = M * ((M + 63) / 64) * sizeof(unsigned long long);
-  const size_t moff = (ints + body + 7) & ~(size_t)7;
-  A.lds_mask_off = (D.C > 1 && body > 0 && moff + maskb <= 159 * 1024) ? moff : 0;
-  const int threads = M > 48 ? 1024 : 256;
-  hipLaunchKernelGGL(k_moe_solve, dim3(D.K), dim3(threads), A.lds_mask_off ? moff + maskb : ints + body, L.stream, D, A);
+// A: filled by the host, its three lds_* values from this plan (plan_ridge_launch of ridge_geom, RidgeKind::Solve)
+RidgeLaunch l_moe_solve(const Launch& L, const Dev& D, const SolveArgs& A) {
+  RidgeLaunch t = plan_ridge_launch(ridge_geom(D, L), RidgeKind::Solve);
+  if (t.valid) HMX_RIDGE_LAUNCH(k_moe_solve, D, A);
+  return t;
 }
-void l_moe_stats_mfma(const Launch& L, const Dev& D) {
-  const int npt = (D.d + 15) / 16;
-  if (D.st_dma) {   // 16-byte operand loads + deterministic slot reduction (K <= 128)
-    const dim3 grid((unsigned)D.st_nwg, (unsigned)D.st_halves), block(64 * ((D.d + 16) / 16));   // PC tiles incl. the ones column at index d; y: the halves of the clusters (K > 128)
-    const int nct_q = D.st_halves == 2 ? (D.st_KH + 15) / 16 : D.NCT;
-    // (round 6) fp64 shadow sums in LDS + operands one tile ahead where two workgroups still fit a CU next to them (else the round-3 form)
-    const size_t shl = (size_t)(block.x / 64) * nct_q * 4 * 64 * sizeof(double);
-    const bool use_shl = 2 * shl <= LDS_BUDGET;
-#define HMX_MSQ(N) case N: if (use_shl) hipLaunchKernelGGL((k_moe_stats_q<N, true>), grid, block, shl, L.stream, D, D.st_cpw); \
-                           else hipLaunchKernelGGL((k_moe_stats_q<N>), grid, block, 0, L.stream, D, D.st_cpw); break;
-    switch (nct_q) { HMX_MSQ(1) HMX_MSQ(2) HMX_MSQ(3) HMX_MSQ(4) HMX_MSQ(5) HMX_MSQ(6) HMX_MSQ(7) HMX_MSQ(8) default: break; }
-#undef HMX_MSQ
-    const size_t per = (size_t)D.K * D.d + D.K;
-    hipLaunchKernelGGL(k_moe_stats_reduce, dim3((unsigned)D.Q, (unsigned)((per + 255) / 256)), dim3(256), 0, L.stream, D);
-    return;
-  }
-  int tpw = (D.ntitems + 2 * 256 - 1) / (2 * 256);   // ~2 workgroups per CU
-  if (tpw < 16) tpw = 16;
-  const bool split = D.NCT > 8;                       // K > 128: two workgroups (cluster-tile halves) per tile range
-  const dim3 grid(((D.ntitems + tpw - 1) / tpw) * (split ? 2 : 1)), block(64 * npt);
-#define HMX_MS(N) case N: hipLaunchKernelGGL((k_moe_stats_mfma<N, 1>), grid, block, 0, L.stream, D, tpw, npt); break;
-#define HMX_MS2(N) case N: hipLaunchKernelGGL((k_moe_stats_mfma<N, 2>), grid, block, 0, L.stream, D, tpw, npt); break;
-  switch (D.NCT) {
-    HMX_MS(1) HMX_MS(2) HMX_MS(3) HMX_MS(4) HMX_MS(5) HMX_MS(6) HMX_MS(7) HMX_MS(8)
-    HMX_MS2(10) HMX_MS2(12) HMX_MS2(13) HMX_MS2(14) HMX_MS2(16)
-    default: break;
-  }
-#undef HMX_MS
-#undef HMX_MS2
-}
-void l_moe_apply_mfma(const Launch& L, const Dev& D) {
-  int g = D.naitems < 4 * L.grid ? D.naitems : 4 * L.grid;
-  if (g < 1) g = 1;
-  const dim3 grid(g);
-  const size_t lds = (size_t)D.wNQ * D.wNS * 64 * sizeof(f32x4);
-  switch ((D.d + 15) / 16) {
-    case 1: hipLaunchKernelGGL(k_moe_apply_mfma<1>, grid, dim3(256), lds, L.stream, D); break;
-    case 2: hipLaunchKernelGGL(k_moe_apply_mfma<2>, grid, dim3(256), lds, L.stream, D); break;
-    case 3: hipLaunchKernelGGL(k_moe_apply_mfma<3>, grid, dim3(256), lds, L.stream, D); break;
-    default: hipLaunchKernelGGL(k_moe_apply_mfma<4>, grid, dim3(256), lds, L.stream, D); break;
-  }
+RidgeLaunch l_moe_apply(const Launch& L, const Dev& D) {
+  RidgeLaunch t = plan_ridge_launch(ridge_geom(D, L), RidgeKind::Apply);
+  if (!t.valid) return t;
+#define HMX_MA_CASE(KPL, DPL) case 2 * KPL + DPL: HMX_RIDGE_LAUNCH((k_moe_apply<KPL, DPL>), D); return t;
+#define HMX_MAM_CASE(NPT) case NPT: HMX_RIDGE_LAUNCH(k_moe_apply_mfma<NPT>, D); return t;
+  if (!t.mfma) switch (2 * t.p0 + t.p1) { HMX_RIDGE_APPLY_TUPLES(HMX_MA_CASE) default: break; }
+  else switch (t.p0) { HMX_RIDGE_APPLY_MFMA_TUPLES(HMX_MAM_CASE) default: break; }
+#undef HMX_MA_CASE
+#undef HMX_MAM_CASE
+  t.valid = false;
+  return t;
 }
 void l_seed_race_u(const Launch& L, const Dev& D, const float* u, int a0, int na, int only, uint64_t goff, const unsigned* excl,
                    int nexcl) {

@@ -27,7 +27,6 @@ struct Switches {
   bool sold_carry_set = false, sold_carry = false;       // HMX_SOLD_CARRY=0|1
   int shuffle_inv = 1;                                   // HMX_SHUFFLE_INV: 0 counting sort always; 2 sort-free form on sharded runs too
   bool solve_host = false;                               // HMX_MOE_SOLVE=host
-  bool stats_atomic = false;                             // HMX_MOE_STATS=atomic
   bool fused_fold_off = false;                           // HMX_FUSED_FOLD=0
   int fold_impl = 0;                                     // HMX_FOLD_IMPL=split|merged -> 1 | 2: force the two-kernel fold + penalty / k_foldpen of the step loop (tests)
   int chain = -1, chain_pair = -1;                       // HMX_CHAIN / HMX_CHAIN_PAIR: 0 off | 1 forced | -1 (unset, anything else) by the thresholds
@@ -55,7 +54,6 @@ inline Switches read_switches() {
   if ((e = getenv("HMX_SOLD_CARRY"))) { s.sold_carry_set = true; s.sold_carry = atoi(e) == 1; }
   if ((e = getenv("HMX_SHUFFLE_INV"))) s.shuffle_inv = atoi(e);
   s.solve_host = is(getenv("HMX_MOE_SOLVE"), "host");
-  s.stats_atomic = is(getenv("HMX_MOE_STATS"), "atomic");
   s.fused_fold_off = is(getenv("HMX_FUSED_FOLD"), "0");
   e = getenv("HMX_FOLD_IMPL"); s.fold_impl = is(e, "split") ? 1 : is(e, "merged") ? 2 : 0;
   s.chain = tri(getenv("HMX_CHAIN"));
@@ -99,7 +97,9 @@ constexpr int64_t CARRY_PAD_PER_KEY = 8, CARRY_CELLS_PER_PAD = 8;
 constexpr size_t LDS_PER_CU = 160 * 1024;           // LDS of a compute unit: what the workgroups resident on it share
 constexpr size_t LDS_BUDGET = 150 * 1024;           // what the workgroup(s) owning a CU ask for at most: its LDS less room for the kernels' static objects
 constexpr size_t FOLD_LDS_BYTES = LDS_BUDGET, FOLD_LDS_SLACK = 64;       // LDS a tile kernel with the fold in its prologue (fused fold, both chains) may take, less its static words
-constexpr size_t SOLVE_LDS_BYTES = 158 * 1024;      // LDS panel of the device Cholesky
+// device ridge solve (k_moe_solve): index words + body (Cholesky panel or, where they fit beside the index words in SOLVE_RHS_LDS_BYTES, the d right-hand sides) within
+// SOLVE_LDS_BYTES; the coupling masks of the Schur complement ride behind them while the whole stays within SOLVE_MASK_LDS_BYTES
+constexpr size_t SOLVE_LDS_BYTES = 158 * 1024, SOLVE_RHS_LDS_BYTES = LDS_BUDGET, SOLVE_MASK_LDS_BYTES = 159 * 1024;
 constexpr int64_t INT32_CELLS = 2147483000ll;       // positions of a padded block order are int32
 // the launch-per-step path gives a wave a contiguous range of a block's tiles once it has several tiles per block
 constexpr double CONTIG_MIN_TILES_PER_WAVE = 4.0;
@@ -142,6 +142,15 @@ inline size_t pair_folder_bytes(int B, int kw) { return ((size_t)2 * B * kw + kw
 inline bool fold_lds_fits(const Plan& p, const Shape& s) { return image_bytes_f32(p.NQ, p.NS) + fold_table_bytes(s.B, s.K, s.Q, s.C, true, true, false) + FOLD_LDS_SLACK <= FOLD_LDS_BYTES; }
 // Lloyd on the tile kernel: the fp32 image and the sum table fit a CU's LDS (else k_lloyd sums into memory)
 inline bool lloyd_tile_fits(int NQ, int NS, int K, int d) { return image_bytes_f32(NQ, NS) + lloyd_sum_bytes(K, d) <= LDS_PER_CU; }
+
+// ---- the LDS of a k_moe_solve launch, term by term (plan_shape's envelope and plan_ridge_launch are sums of these) ------------------------------
+// index words in front of the fp64 space: row_of, keepl, okb [B] each, misc [4 + C], prow [B + 1], rounded up to an even count (the kernel's PAN_OFF).  envelope: the
+// budget of solve_on_device was written as 4 B + 8 + C words without that rounding and keeps its value -- 8 or 12 bytes MORE than a launch takes, so every admitted
+// shape's launch fits, and no shape flips: with either formula the last B admitted is 1122 (for every C <= 16), 1123 is 72 bytes and more over.
+inline size_t solve_index_bytes(int B, int C, bool envelope) { return (envelope ? (size_t)4 * B + 8 + C : ((size_t)4 * B + 6 + C) & ~(size_t)1) * sizeof(int); }
+inline size_t solve_panel_bytes(int B) { return ((size_t)B + 1) * 16 * sizeof(double); }                  // Cholesky panel: 16 columns of M = B + 1 rows
+inline size_t solve_rhs_bytes(int B, int d) { return ((size_t)B + 1) * d * sizeof(double); }              // the d right-hand sides, during the substitution
+inline size_t solve_mask_bytes(int B) { return ((size_t)B + 1) * (((size_t)B + 1 + 63) / 64) * 8; }       // coupling masks: one bit per (row, eliminated level)
 
 // Stage 1: everything up to this rank's view of fused_ok / chain_ok.  (Sharded runs then agree on the minimum of both flags.)
 inline Plan plan_shape(const Switches& sw, const Shape& s) {
@@ -190,13 +199,13 @@ inline Plan plan_shape(const Switches& sw, const Shape& s) {
   p.shuf_inv = sw.shuffle_inv != 0 && (s.world == 1 || sw.shuffle_inv == 2) && p.carry_ok &&      /* (without the carry every round needs D.blk: the counting sort has it for free) */
                s.nb < 64 && Q < 2048 && s.N_global < ((int64_t)1 << 31) &&
                ((size_t)s.nb * Q + (size_t)Q + 1) * sizeof(int) + 5 * 4096 <= 64 * 1024;
-  p.solve_on_device = !sw.solve_host && (size_t)(B + 1) * 16 * 8 + (size_t)(4 * B + 8 + C) * 4 <= SOLVE_LDS_BYTES;
+  p.solve_on_device = !sw.solve_host && solve_index_bytes(B, C, true) + solve_panel_bytes(B) <= SOLVE_LDS_BYTES;
   // deterministic statistics pass (k_moe_stats_q): static split of the 16-cell tiles over ~2 workgroups per CU
-  // (round 6: K in (128, 224] -- configs[4]'s 200 -- as two halves of <= 8 cluster tiles each, by the same kernel: deterministic there too, and 0.26 ms per
-  //  correction faster than the fp64-atomic kernel at 1M cells)
+  // (round 6: K in (128, 256] -- configs[4]'s 200 -- as two halves of <= 8 cluster tiles each, by the same kernel: deterministic there too.  Every shape with
+  //  moe_mfma takes it -- K % 4 == 0 and K <= 256 give NCT <= 8 or two such halves -- so st_dma == moe_mfma; the fp64-atomic kernel it replaced is gone)
   p.st_KH = ((K + 1) / 2 + 3) & ~3;
   p.st_halves = (p.NCT > 8 && K % 4 == 0 && (p.st_KH + 15) / 16 <= 8 && K - p.st_KH >= 4 && K - p.st_KH <= 16 * ((p.st_KH + 15) / 16)) ? 2 : 1;
-  p.st_dma = (p.moe_mfma && (p.NCT <= 8 || p.st_halves == 2) && !sw.stats_atomic) ? 1 : 0;
+  p.st_dma = (p.moe_mfma && (p.NCT <= 8 || p.st_halves == 2)) ? 1 : 0;
   if (p.st_dma) { p.st_cpw = std::max(16, (s.ntitems + 2 * 256 - 1) / (2 * 256)); p.st_nwg = (s.ntitems + p.st_cpw - 1) / p.st_cpw; }
   p.fused_ok = !sw.fused_fold_off && fold_lds_fits(p, s);
   // persistent block chain: one workgroup per CU must be resident at once (they synchronise inside the launch)
@@ -308,6 +317,59 @@ inline TileLaunch plan_tile_launch(const TileGeom& g, TileKind kind, int workgro
   }
   if (t.mode != 6) t.lds = (t.bf ? image_bytes_bf(g.NCT, g.NS2) : image_bytes_f32(g.NQ, g.NS)) + rest;
   t.blocks = (int)blocks; t.valid = t.lds <= LDS_PER_CU && t.blocks >= 1;
+  return t;
+}
+
+// ---- one launch of the ridge correction (moe_correct_ridge): statistics, device solve, apply -- a pure function of the scalar fields of Dev and Launch its
+// launchers decide on (hmx_k_launch.inc: ridge_geom)
+struct RidgeGeom {
+  int K = 0, KP = 0, d = 0, B = 0, C = 0, Q = 0, NCT = 0;
+  int moe_mfma = 0, st_dma = 0, st_halves = 1, st_KH = 0, st_nwg = 0, wNQ = 0, wNS = 0;
+  int nitems = 0, naitems = 0, grid = 2048;      // static work lists of <= 256 / <= 1024 cells; workgroups of the streaming kernels (Launch::grid)
+};
+enum class RidgeKind { Stats = 0, Solve = 1, Apply = 2 };
+constexpr const char* RIDGE_KIND_NAME[3] = {"stats", "solve", "apply"};
+// mfma = false: the first-generation kernels k_moe_stats<p0 = DP> / k_moe_apply<p0 = KPL, p1 = DPL>; true: k_moe_stats_q<p0 = cluster tiles of a half or of the whole,
+// p1 = SHL> (+ k_moe_stats_reduce on rgx x rgy workgroups behind it) / k_moe_apply_mfma<p0 = NPT>.  The solve is one kernel (mfma: it also writes the table's MFMA image);
+// its three lds_* values go into SolveArgs.  valid = false: nothing may be launched (LDS over the limit, or no instantiation for the parameters).
+struct RidgeLaunch {
+  bool valid = false, mfma = false; int p0 = 0, p1 = 0, gx = 1, gy = 1, gz = 1, threads = 0; size_t lds = 0;
+  size_t lds_b_bytes = 0, lds_body_bytes = 0, lds_mask_off = 0; int rgx = 0, rgy = 0;
+};
+inline RidgeLaunch plan_ridge_launch(const RidgeGeom& g, RidgeKind kind) {
+  RidgeLaunch t; t.mfma = g.moe_mfma != 0;
+  if (g.K < 1 || g.d < 1) return t;
+  const auto clamp = [](long long v, long long hi) { return (int)std::max<long long>(1, std::min(v, hi)); };
+  if (kind == RidgeKind::Solve) {      // one workgroup per cluster
+    const size_t ints = solve_index_bytes(g.B, g.C, false), panel = solve_panel_bytes(g.B), ball = solve_rhs_bytes(g.B, g.d);
+    // the d right-hand sides live in LDS during the substitution where they fit the budget beside the index words -- or the panel's space anyway (d <= 16)
+    const size_t body = ints + ball <= SOLVE_RHS_LDS_BYTES ? std::max(panel, ball) : panel;
+    t.lds_b_bytes = body >= ball ? ball : 0; t.lds_body_bytes = body; t.lds = ints + body;
+    // coupling masks of the Schur complement -- only with several covariates, and only while they are small
+    const size_t moff = (ints + body + 7) & ~(size_t)7, maskb = solve_mask_bytes(g.B);
+    if (g.C > 1 && moff + maskb <= SOLVE_MASK_LDS_BYTES) { t.lds_mask_off = moff; t.lds = moff + maskb; }
+    t.gx = g.K; t.threads = g.B + 1 > 48 ? 1024 : 256;
+    t.valid = ints + body <= SOLVE_LDS_BYTES;      // (plan_shape: solve_on_device admits no shape beyond it)
+  } else if (kind == RidgeKind::Stats && t.mfma) {
+    // slot form: 16-byte operand loads + deterministic slot reduction; a wave per PC tile incl. the ones column at index d; y: the halves of the clusters (K > 128)
+    t.p0 = g.st_halves == 2 ? (g.st_KH + 15) / 16 : g.NCT;
+    t.gx = g.st_nwg; t.gy = g.st_halves; t.threads = 64 * ((g.d + 16) / 16);
+    // (round 6) fp64 shadow sums in LDS + operands one tile ahead where two workgroups still fit a CU next to them (else the round-3 form)
+    const size_t shl = (size_t)(t.threads / 64) * t.p0 * 4 * 64 * sizeof(double);
+    t.p1 = 2 * shl <= LDS_BUDGET ? 1 : 0; t.lds = t.p1 ? shl : 0;
+    t.rgx = g.Q; t.rgy = (int)(((size_t)g.K * g.d + g.K + 255) / 256);
+    t.valid = g.st_dma && t.p0 >= 1 && t.p0 <= 8 && t.threads <= 320 && t.gx >= 1;
+  } else if (kind == RidgeKind::Stats) {      // first generation: PCs in chunks of DP <= 32 (grid.z), 128 clusters per grid.y
+    const int zch = (g.d + 31) / 32;
+    t.p0 = ((g.d + zch - 1) / zch + 3) / 4 * 4;
+    t.gx = clamp(((long long)g.nitems + 3) / 4, g.grid); t.gy = (g.K + 127) / 128; t.gz = (g.d + t.p0 - 1) / t.p0; t.threads = 256;
+    t.valid = t.p0 >= 4 && t.p0 <= 32;
+  } else {      // apply: one workgroup per apply item, at most four per streaming workgroup
+    t.gx = clamp(g.naitems, 4ll * g.grid); t.threads = 256;
+    if (t.mfma) { t.p0 = (g.d + 15) / 16; t.lds = (size_t)g.wNQ * g.wNS * 1024; t.valid = t.p0 >= 1 && t.p0 <= 4; }      // the table's image of one combination
+    else { t.p0 = g.KP / 64; t.p1 = g.d > 64 ? 2 : 1; t.lds = (size_t)g.K * 64 * t.p1 * sizeof(float); t.valid = t.p0 >= 1 && t.p0 <= 4 && g.d <= 128; }
+    t.valid = t.valid && t.lds <= LDS_PER_CU;
+  }
   return t;
 }
 

@@ -41,6 +41,11 @@ extern "C" {
  *   the last k_tile launch of a kind as it ran (plan_tile_launch, harmony_amd/csrc/hmx_plan.h): "launch:head" "launch:lloyd" "launch:seed" "launch:update"
  *   "launch:chain" -- 9 doubles: valid, bf (1: split-bf16 build), nct, mode, wps, usig (the instantiation k_tile<nct, mode, wps, usig>), threads, blocks,
  *   lds (bytes); -1 while the handle has not made a launch of that kind since hmx_setup;
+ *   the last launch of the ridge correction of a kind as it ran (plan_ridge_launch, harmony_amd/csrc/hmx_plan.h): "launch:stats" "launch:solve" "launch:apply"
+ *   -- 14 doubles: valid, mfma (0: the first-generation kernels), p0, p1 (the instantiation: k_moe_stats<p0 = DP> | k_moe_stats_q<p0 = cluster tiles of a half
+ *   or of the whole, p1 = fp64 shadows in LDS> for stats, k_moe_apply<p0 = KPL, p1 = DPL> | k_moe_apply_mfma<p0 = NPT> for apply, none for solve), grid x, y, z,
+ *   threads, lds (bytes), the solve's lds_b_bytes, lds_body_bytes, lds_mask_off (SolveArgs), grid x, y of k_moe_stats_reduce behind the slot statistics; -1 before
+ *   the first moe_correct_ridge, and for "launch:stats" on a ridge_arith handle (its statistics are the sequential passes);
  *   the plan of the last clustering round (plan_round, harmony_amd/csrc/hmx_round.h): "round:last" -- 8 doubles: path (0 persistent chain, 1 fold in the
  *   update launch's prologue, 2 step loop), merged (step loop: k_foldpen instead of k_fold + k_penalty), chain_tail (the chain closed the round itself),
  *   carried (old contributions filed by the pass before: no pass over R), write_next (it filed the next round's), r_store (0: its R rows were not

@@ -31,7 +31,32 @@ static void launch_row(const hmx::Shape& s, const hmx::Plan& p, int kind, int wo
   const long long f[] = {t.valid, t.bf, t.nct, t.mode, t.wps, t.usig, t.threads, t.blocks, (long long)t.lds};
   for (int i = 0; i < 9; i++) out[1 + i] = f[i];
 }
+// the geometry hmx_setup writes into Dev / Launch for this plan (RIDGE_GEOM of tests/test_plan_cpu.py); nitems / naitems: the static work lists of <= 256 / <= 1024 cells
+static void ridge_geom_row(const hmx::Shape& s, const hmx::Plan& p, int nitems, int naitems, long long* g) {
+  const long long f[] = {s.K, p.KP, s.d, s.B, s.C, s.Q, p.NCT, p.moe_mfma, p.st_dma, p.st_halves, p.st_KH, p.st_nwg, p.wNQ, p.wNS, nitems, naitems, s.grid};
+  for (int i = 0; i < 17; i++) g[i] = f[i];
+}
+static hmx::RidgeGeom ridge_geom_of(const long long* g) {
+  hmx::RidgeGeom r;
+  r.K = (int)g[0]; r.KP = (int)g[1]; r.d = (int)g[2]; r.B = (int)g[3]; r.C = (int)g[4]; r.Q = (int)g[5]; r.NCT = (int)g[6]; r.moe_mfma = (int)g[7]; r.st_dma = (int)g[8];
+  r.st_halves = (int)g[9]; r.st_KH = (int)g[10]; r.st_nwg = (int)g[11]; r.wNQ = (int)g[12]; r.wNS = (int)g[13]; r.nitems = (int)g[14]; r.naitems = (int)g[15]; r.grid = (int)g[16];
+  return r;
+}
 extern "C" {
+// the ridge correction: the geometry of the shape's plan (returns 1 when the plan refuses the shape; solve_on_device: the plan's) ...
+int probe_ridge_geom(const long long* v, int nitems, int naitems, long long* geom, int* solve_on_device) {
+  const hmx::Shape s = shape_of(v);
+  const hmx::Plan p = hmx::plan_unsharded(hmx::read_switches(), s);
+  if (p.limit) return 1;
+  ridge_geom_row(s, p, nitems, naitems, geom); *solve_on_device = p.solve_on_device;
+  return 0;
+}
+// ... and one launch of a geometry (kind = RidgeKind): out = RIDGE_FIELDS of tests/test_plan_cpu.py
+void probe_ridge_launch(const long long* geom, int kind, long long* out) {
+  const hmx::RidgeLaunch t = hmx::plan_ridge_launch(ridge_geom_of(geom), (hmx::RidgeKind)kind);
+  const long long f[] = {t.valid, t.mfma, t.p0, t.p1, t.gx, t.gy, t.gz, t.threads, (long long)t.lds, (long long)t.lds_b_bytes, (long long)t.lds_body_bytes, (long long)t.lds_mask_off, t.rgx, t.rgy};
+  for (int i = 0; i < 14; i++) out[i] = f[i];
+}
 // one k_tile launch of the shape's plan: kind = TileKind, workgroups = the chain's; out: 10 values (launch_row); returns 1 when the plan refuses the shape
 int probe_tile_launch(const long long* v, int kind, int workgroups, int r_store, int fused_fold, long long* out) {
   const hmx::Shape s = shape_of(v);

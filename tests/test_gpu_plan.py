@@ -1,6 +1,7 @@
 """The plan tests/test_plan_cpu.py checks on the CPU IS the plan the library runs: for shapes the suite sets up elsewhere, the path flags of a
 live handle equal what the probe of harmony_amd/csrc/hmx_plan.h returns for the same shape and the device's real CU count -- and every k_tile
-launch the handle then makes (hmx_get "launch:<kind>") is, field by field, the launch the probe plans for it."""
+launch the handle then makes, and every launch of the ridge correction behind them (hmx_get "launch:<kind>"), is, field by field, the launch the
+probe plans for it."""
 import os
 import sys
 
@@ -10,7 +11,7 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from harmony_amd import Harmony, HarmonyError, prepare_setup_args  # noqa: E402
 from helpers import synth  # noqa: E402
-from test_plan_cpu import LAUNCH_FIELDS, plan, tile_launch  # noqa: E402
+from test_plan_cpu import LAUNCH_FIELDS, RIDGE_FIELDS, plan, ridge_launch, tile_launch  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -22,6 +23,10 @@ CASES = {                               # N, d, levels, K, sigma[, environment]
     "sigma_vector": (6000, 30, (4,), 40, "vector"),
     "d68": (20000, 68, (4,), 100, 0.1),                 # (rows of 68 PCs: the split-bf16 form is not offered, every launch is of the fp32 build)
     "uniform_K100_dot_f32": (300000, 50, (10,), 100, 0.1, {"HMX_DOT": "f32"}),
+    # the correction's branches the cases above miss: five waves x 8 cluster tiles of fp64 shadows do not fit LDS twice (slot statistics without them);
+    # 1100 levels: the right-hand sides stay outside LDS, body = the Cholesky panel, 1024 threads (tests/test_gpu_stage_spec.py: h_device_1100)
+    "d64_K128_no_lds_shadows": (20000, 64, (4,), 128, 0.1),
+    "levels_1100_device_solve": (60000, 30, (1100,), 40, 0.1),
 }
 
 
@@ -72,6 +77,29 @@ def test_live_handle_runs_the_probed_plan(name, monkeypatch):
         runs = t.pop("ran") and kind != ("update" if on_chain else "chain")
         assert got[kind] == (t if runs else None), (name, kind, got[kind], t)
     assert got["head"] and got["seed"] and (got["chain"] if on_chain else got["update"]), (name, got)
+
+    # the ridge correction behind the clustering call: statistics, device solve, apply
+    def ridge_ran(kind):
+        try:
+            return dict(zip(RIDGE_FIELDS, (int(v) for v in h._get("launch:" + kind))))
+        except HarmonyError:
+            return None
+
+    assert all(ridge_ran(k) is None for k in ("stats", "solve", "apply")), "no launch of the correction before moe_correct_ridge_cpp"
+    h.moe_correct_ridge_cpp()
+    items = dict(nitems=int(((counts + 255) // 256).sum()), naitems=int(((counts + 1023) // 1024).sum()))      # static work lists: <= 256 / <= 1024 cells of one combination
+    rgot = {k: ridge_ran(k) for k in ("stats", "solve", "apply")}
+    print("RIDGE", name, rgot)
+    for kind in ("stats", "solve", "apply"):
+        t = ridge_launch(kind, N, K, **items, **shape)
+        assert t.pop("solve_on_device") == 1 and t["valid"] == 1, (name, kind, t)
+        assert rgot[kind] == t, (name, kind, rgot[kind], t)
+    want_form = {"d64_K128_no_lds_shadows": ("stats", dict(mfma=1, p0=8, p1=0, threads=320, lds=0)),
+                 "levels_1100_device_solve": ("solve", dict(threads=1024, lds_b_bytes=0, lds_body_bytes=1101 * 128, lds=158552)),
+                 "K200_three_covariates": ("stats", dict(mfma=1, gy=2, p0=7)), "K_not_multiple_of_4": ("stats", dict(mfma=0)), "d68": ("apply", dict(mfma=0, p1=2))}
+    if name in want_form:               # the branch the case is here for
+        kind, fields = want_form[name]
+        assert {k: rgot[kind][k] for k in fields} == fields, (name, rgot[kind])
 
 
 # ---- the round plan (harmony_amd/csrc/hmx_round.h): what the handle's last round decided is what the CPU probe plans for it ---------------------------

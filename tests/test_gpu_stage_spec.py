@@ -104,7 +104,7 @@ def _case(name, cus=256):
         return Z, meta, ["cov0", "cov1"], dict(nclust=40, lambda_=[1.0, 2.0], sigma=sig, theta=[2.0, 0.0]), o, 14, dict(usig=0, host=0)
     if name == "l_forced_fallbacks":
         Z, meta, _ = synth(30000, d=50, levels=(10,), seed=1)
-        env = {"HMX_MOE_SOLVE": "host", "HMX_MOE_IMPL": "v1", "HMX_MOE_STATS": "atomic", "HMX_FUSED_FOLD": "0", "HMX_CHAIN": "0"}
+        env = {"HMX_MOE_SOLVE": "host", "HMX_MOE_IMPL": "v1", "HMX_FUSED_FOLD": "0", "HMX_CHAIN": "0"}
         return Z, meta, "cov0", dict(nclust=100), env, 3, dict(chain=0, host=1)
     if name == "m_block_0.3_prime_pushed":
         Z, meta, _ = synth(20011, d=30, levels=(6,), seed=15)

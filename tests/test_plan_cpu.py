@@ -124,7 +124,7 @@ def test_limits():
     ({"HMX_DOT": "f32"}, dict(N=1000000, **C4), {"dot_bf": (1, 0), "chain_pair": (1, 0), "nrep": (1, 8)}),      # (the pair chain exists in the split-bf16 build only)
     ({"HMX_USIG": "0"}, dict(N=1000000, K=100), {"usig": (1, 0)}),
     ({"HMX_USIG": "0"}, dict(N=1000000, K=64), {"usig": (1, 0), "upd_wps": (4, 2), "upd_threads": (1024, 512)}),
-    ({"HMX_MOE_STATS": "atomic"}, dict(N=1000000, K=100), {"st_dma": (1, 0), "st_cpw": (123, 0), "st_nwg": (509, 0)}),      # (62 500 tiles over 512 workgroups: 123 each)
+    ({"HMX_MOE_STATS": "atomic"}, dict(N=1000000, K=100), {}),      # (retired with the fp64-atomic statistics kernel: the slot form -- 62 500 tiles over 512 workgroups, 123 each -- stays)
     ({"HMX_MOE_SOLVE": "host"}, dict(N=1000000, K=100), {"solve_on_device": (1, 0)}),
     ({"HMX_SHUFFLE_INV": "0"}, dict(N=1000000, K=100), {"shuf_inv": (1, 0)}),
     ({"HMX_SHUFFLE_INV": "2"}, dict(N=1000000, K=100), {}),
@@ -138,6 +138,8 @@ def test_forcing_switch_flips_the_decision_it_documents(monkeypatch, env, shape,
         monkeypatch.setenv(k, v)
     forced = plan(**shape)
     assert {k: (base[k], forced[k]) for k in diff(base, forced)} == flips
+    if "HMX_MOE_STATS" in env:
+        assert (forced["st_dma"], forced["st_cpw"], forced["st_nwg"]) == (1, 123, 509)
 
 
 # ---- one k_tile launch (plan_tile_launch): which instantiation, of which build, on what grid, with how much LDS -------------------------------
@@ -268,3 +270,115 @@ def test_every_planned_launch_of_the_envelope_is_a_kernel_of_the_build(monkeypat
     for bf, nct, mode, wps, usig in unreached:
         print("  %s k_tile<%d, %d, %d, %s, %s>" % ("hmx_tile_bf" if bf else "hmx_kernels", nct, mode, wps, str(bool(usig)).lower(), str(bool(bf)).lower()))
     assert n > 1000000
+
+
+# ---- one launch of the ridge correction (plan_ridge_launch): which kernel of which form, on what grid, with how much LDS ------------------------------------
+RIDGE_KINDS = {"stats": 0, "solve": 1, "apply": 2}
+RIDGE_GEOM = ("K", "KP", "d", "B", "C", "Q", "NCT", "moe_mfma", "st_dma", "st_halves", "st_KH", "st_nwg", "wNQ", "wNS", "nitems", "naitems", "grid")
+RIDGE_FIELDS = ("valid", "mfma", "p0", "p1", "gx", "gy", "gz", "threads", "lds", "lds_b_bytes", "lds_body_bytes", "lds_mask_off", "rgx", "rgy")
+
+
+def ridge_launch(kind, N, K, nitems=None, naitems=None, forge=None, **kw):
+    """the correction's launch of one kind for a shape, as a dict of RIDGE_FIELDS + "solve_on_device" (the plan's); None: plan limit.  nitems / naitems: the static
+    work lists of <= 256 / <= 1024 cells (default: one combination's); forge: geometry fields overwritten after the plan (shapes hmx_setup never produces)"""
+    lib = plan_probe()
+    lib.probe_ridge_geom.argtypes = [C.POINTER(C.c_longlong), C.c_int, C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_int)]
+    lib.probe_ridge_launch.argtypes = [C.POINTER(C.c_longlong), C.c_int, C.POINTER(C.c_longlong)]
+    lib.probe_ridge_launch.restype = None
+    geom, sod, out = (C.c_longlong * len(RIDGE_GEOM))(), C.c_int(0), (C.c_longlong * len(RIDGE_FIELDS))()
+    if lib.probe_ridge_geom(shape_vector(N, K, **kw), (N + 255) // 256 if nitems is None else nitems, (N + 1023) // 1024 if naitems is None else naitems, geom, C.byref(sod)):
+        return None
+    for k, v in (forge or {}).items():
+        geom[RIDGE_GEOM.index(k)] = v
+    lib.probe_ridge_launch(geom, RIDGE_KINDS[kind], out)
+    return dict(zip(RIDGE_FIELDS, out), solve_on_device=sod.value)
+
+
+def ridge(mfma, p0, p1, grid, threads, lds, solve=(0, 0, 0), reduce=(0, 0), valid=1):
+    gx, gy, gz = grid
+    return dict(valid=valid, mfma=mfma, p0=p0, p1=p1, gx=gx, gy=gy, gz=gz, threads=threads, lds=lds, lds_b_bytes=solve[0], lds_body_bytes=solve[1], lds_mask_off=solve[2],
+                rgx=reduce[0], rgy=reduce[1], solve_on_device=1)
+
+
+def test_ridge_solve_lds_terms():
+    """l_moe_solve's expressions: index words ((4B + 6 + C) & ~1) * 4, panel (B + 1) * 16 * 8, right-hand sides (B + 1) * d * 8 -- in LDS while index words + them are within
+    150 KB --, body = the larger; masks (B + 1) * ceil((B + 1) / 64) * 8 behind the body rounded up to 8, for C > 1 within 159 KB; 1024 threads from 49 rows on; one workgroup per cluster"""
+    # B = 10, C = 1, d = 50: (46 & ~1) * 4 = 184; panel 11 * 128 = 1408 < right-hand sides 11 * 400 = 4400; no masks
+    assert ridge_launch("solve", 100000, 100, B=10) == ridge(1, 0, 0, (100, 1, 1), 256, 184 + 4400, solve=(4400, 4400, 0))
+    # B = 200, C = 3, d = 50: (809 & ~1) * 4 = 3232; right-hand sides 201 * 400 = 80400 > panel 25728; masks 201 * 4 * 8 = 6432 at (3232 + 80400 + 7) & ~7 = 83632
+    assert ridge_launch("solve", 1000000, **C4) == ridge(1, 0, 0, (200, 1, 1), 1024, 83632 + 6432, solve=(80400, 80400, 83632))
+    assert 83632 + 6432 == 90064
+    # B = 1100, C = 1, d = 30: (4407 & ~1) * 4 = 17624; right-hand sides 1101 * 240 = 264240: not in LDS; body = panel 1101 * 128 = 140928
+    assert ridge_launch("solve", 60000, 40, d=30, B=1100) == ridge(1, 0, 0, (40, 1, 1), 1024, 17624 + 140928, solve=(0, 140928, 0))
+    assert 17624 + 140928 == 158552
+    # d = 16, B = 1100: right-hand sides 1101 * 128 = the panel's bytes: beyond 150 KB beside the index words, but they fit the panel's space and stay in LDS
+    assert ridge_launch("solve", 60000, 40, d=16, B=1100) == ridge(1, 0, 0, (40, 1, 1), 1024, 17624 + 140928, solve=(140928, 140928, 0))
+    # threads: B + 1 > 48
+    assert [ridge_launch("solve", 100000, 100, B=B)["threads"] for B in (47, 48)] == [256, 1024]
+    # the envelope (plan_shape: (4B + 8 + C) * 4 + (B + 1) * 128 <= 158 KB = 161792): B = 1122 -> 17956 + 4 + 143744 = 161704 + 4C; B = 1123: 17972 + 4C + 143872 > 161792
+    for C_ in (1, 2, 3, 4):
+        last, first = ridge_launch("solve", 100000, 100, B=1122, C_=C_), ridge_launch("solve", 100000, 100, B=1123, C_=C_)
+        assert (last["solve_on_device"], last["valid"], first["solve_on_device"], first["valid"]) == (1, 1, 0, 0), C_
+    assert ridge_launch("solve", 100000, 100, B=1122)["lds"] == (4495 & ~1) * 4 + 1123 * 128 == 161720
+    assert plan(100000, 100, B=1122)["solve_on_device"] == 1 and plan(100000, 100, B=1123)["solve_on_device"] == 0
+
+
+def test_ridge_statistics_forms():
+    # slot form, l_moe_stats_mfma's st_dma branch: grid (st_nwg, st_halves), a wave per PC tile incl. the ones column: 64 * ((d + 16) / 16) threads; fp64 shadows
+    # [waves][nct * 4][64] doubles in LDS while two workgroups' fit 150 KB; reduce launch (Q, ceil((K d + K) / 256)).  1M cells: 62 500 tiles / 512 -> 123 per workgroup, 509 workgroups
+    assert ridge_launch("stats", 1000000, 100) == ridge(1, 7, 1, (509, 1, 1), 256, 4 * 7 * 2048, reduce=(20, (100 * 50 + 100 + 255) // 256))
+    # K > 128: two halves, st_KH = ((K + 1) / 2 + 3) & ~3 = 100 at K = 200 -> 7 cluster tiles per half, grid.y = 2
+    assert ridge_launch("stats", 1000000, **C4) == ridge(1, 7, 1, (509, 2, 1), 256, 4 * 7 * 2048, reduce=(200, (200 * 50 + 200 + 255) // 256))
+    for K in range(132, 257, 4):
+        t, p = ridge_launch("stats", 100000, K), plan(100000, K)
+        assert (t["valid"], t["gy"], t["p0"]) == (1, 2, (p["st_KH"] + 15) // 16) and p["st_halves"] == 2 and t["p0"] <= 8, K
+    # d = 64: five waves; with 8 cluster tiles 2 * 5 * 8 * 2048 = 163 840 > 153 600: no LDS shadows -- K in 116 .. 128 (whole) and 228 .. 256 (halves of 116 .. 128); 7 tiles: 143 360 fit
+    without = [K for K in range(4, 257, 4) if not ridge_launch("stats", 100000, K, d=64)["p1"]]
+    assert without == list(range(116, 129, 4)) + list(range(228, 257, 4))
+    assert all(ridge_launch("stats", 100000, K, d=64) == dict(ridge_launch("stats", 100000, K, d=64), valid=1, threads=320, lds=0, p0=8) for K in without)
+    assert all(ridge_launch("stats", 100000, K, d=63)["p1"] == 1 and ridge_launch("stats", 100000, K, d=63)["threads"] == 256 for K in range(4, 257, 4))
+    assert ridge_launch("stats", 100000, 128, d=63)["lds"] == 4 * 8 * 2048 and ridge_launch("stats", 100000, 112, d=64)["lds"] == 5 * 7 * 2048
+    # every shape with the MFMA kernels takes the slot form, on an instantiation that exists (1 .. 8 cluster tiles)
+    for K in range(4, 257, 4):
+        for d in (1, 16, 50, 64):
+            t, p = ridge_launch("stats", 100000, K, d=d), plan(100000, K, d=d)
+            assert (p["moe_mfma"], p["st_dma"], t["valid"], t["mfma"]) == (1, 1, 1, 1) and 1 <= t["p0"] <= 8, (K, d)
+    # first generation (l_moe_stats), K = 50 (K % 4 != 0), d = 50: zch = 2 chunks of ceil(50 / 2) = 25 -> DP = 28, grid.z = ceil(50 / 28) = 2; 128 clusters per grid.y;
+    # 100 000 cells: 391 items of 256 cells, four per workgroup -> 98
+    assert ridge_launch("stats", 100000, 50) == ridge(0, 28, 0, (98, 1, 2), 256, 0)
+    assert ridge_launch("stats", 100000, 130, d=128) == ridge(0, 32, 0, (98, 2, 4), 256, 0)      # (d = 128: four chunks of 32)
+    assert ridge_launch("stats", 100000000, 50)["gx"] == 2048                                   # (capped at the streaming grid)
+    # forged geometries: 9 cluster tiles in one half have no instantiation; the MFMA form without its slots (st_dma = 0) has no kernel any more
+    assert ridge_launch("stats", 100000, 100, forge={"NCT": 9})["valid"] == 0
+    assert ridge_launch("stats", 100000, 100, forge={"st_dma": 0})["valid"] == 0
+
+
+def test_ridge_apply_forms():
+    # MFMA form (l_moe_apply_mfma), K = 100: NPT = ceil(d / 16); the image of one combination [wNQ = 1][wNS = 4 * 6 + 1 = 25] KB; 98 apply items of 1024 cells, one workgroup each
+    for d, npt in ((16, 1), (17, 2), (64, 4)):
+        assert ridge_launch("apply", 100000, 100, d=d) == ridge(1, npt, 0, (98, 1, 1), 256, 25 * KB), d
+    # d = 65: the plan takes the first generation (l_moe_apply): KPL = KP / 64 = 2, DPL = 2 (d > 64), K * 64 * DPL floats of LDS
+    assert ridge_launch("apply", 100000, 100, d=65) == ridge(0, 2, 2, (98, 1, 1), 256, 100 * 64 * 2 * 4)
+    assert ridge_launch("apply", 100000, 100, d=65, forge={"moe_mfma": 1})["valid"] == 0      # (NPT = 5: no instantiation)
+    # first generation at K = 50 (KP = 64): DPL = 1 up to d = 64
+    for d, dpl in ((16, 1), (17, 1), (64, 1), (65, 2)):
+        assert ridge_launch("apply", 100000, 50, d=d) == ridge(0, 1, dpl, (98, 1, 1), 256, 50 * 64 * dpl * 4), d
+    assert ridge_launch("apply", 100000000, 100)["gx"] == 4 * 2048 and ridge_launch("apply", 100000, 50, forge={"KP": 320})["valid"] == 0
+
+
+def test_every_planned_ridge_launch_is_a_kernel_of_the_build():
+    """Across K = 1 .. 256 and a spread of d, every statistics / apply launch the plan makes names an instantiation of profiles/r6_kernel_resources.txt"""
+    import re
+    names = set()
+    for line in open(os.path.join(ROOT, "profiles", "r6_kernel_resources.txt")):
+        m = re.match(r"hmx_kernels\s.*\s(k_moe_\w+<[^>]*>)$", line.rstrip())
+        if m:
+            names.add(m.group(1))
+    assert len(names) == 8 + 16 + 8 + 4 and not any(n.startswith("k_moe_stats_mfma") for n in names), sorted(names)
+    for K in range(1, 257):
+        for d in (1, 16, 17, 50, 63, 64, 65, 100, 128):
+            st, ap = ridge_launch("stats", 100000, K, d=d), ridge_launch("apply", 100000, K, d=d)
+            assert st["valid"] and ap["valid"] and ridge_launch("solve", 100000, K, d=d)["valid"], (K, d)
+            want = ("k_moe_stats_q<%d, %s>" % (st["p0"], "true" if st["p1"] else "false") if st["mfma"] else "k_moe_stats<%d>" % st["p0"],
+                    "k_moe_apply_mfma<%d>" % ap["p0"] if ap["mfma"] else "k_moe_apply<%d, %d>" % (ap["p0"], ap["p1"]))
+            assert set(want) <= names, (K, d, want)

@@ -8,8 +8,10 @@ from .harmony_obj import Harmony, HarmonyError
 from .mapping import HarmonyReference, map_query
 from .metrics import compute_lisi, knn, knn_predict, lisi_from_knn
 from .options import harmony_options
+from .silhouette import silhouette_batch, silhouette_label, silhouette_samples
 from .ui import RunHarmony, prepare_setup_args
 from .utils import harmonize
 
 __all__ = ["RunHarmony", "harmony_options", "Harmony", "HarmonyError", "harmonize", "prepare_setup_args", "map_query",
-           "HarmonyReference", "knn", "compute_lisi", "lisi_from_knn", "knn_predict"]
+           "HarmonyReference", "knn", "compute_lisi", "lisi_from_knn", "knn_predict",
+           "silhouette_samples", "silhouette_label", "silhouette_batch"]

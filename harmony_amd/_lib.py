@@ -73,6 +73,11 @@ METRICS_SIGNATURES = {
     "hmx_compute_lisi": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32, _ip, C.c_int32, _ip, C.c_double, _dp]),
 }
 
+# the symbol include/harmony_mi355x_silhouette.h declares (silhouette widths)
+SILHOUETTE_SIGNATURES = {
+    "hmx_silhouette": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32, _ip, C.c_int32, _ip, C.c_int32, _dp, _dp, _dp]),
+}
+
 _lib = None
 
 
@@ -90,7 +95,7 @@ def load():
             "libharmony_mi355x.so is not built (%s). Run `python -m harmony_amd.build`; "
             "harmony_amd has no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(METRICS_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(METRICS_SIGNATURES.items()) + list(SILHOUETTE_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the ABI and the header drift apart
         fn.restype = res
         fn.argtypes = args

@@ -4,6 +4,7 @@
 // kernel (hmx_kernels.hip) and all per-cell state stays in HBM between calls.
 #include "../../include/harmony_mi355x_lab.h"      // (the reference interface + the probes / tuning declarations: the library defines both)
 #include "../../include/harmony_mi355x_metrics.h"  // (kNN / LISI: hmx_api_metrics.inc)
+#include "../../include/harmony_mi355x_silhouette.h"  // (silhouette widths: hmx_api_silhouette.inc)
 #include "hmx_internal.h"
 #include "hmx_rrng.h"
 #include "hmx_plan.h"
@@ -351,3 +352,4 @@ int hmx_moe_correct_ridge(hmx_ctx* ctx) {  // src/harmony.cpp:345-638
 
 #include "hmx_api_diag.inc"
 #include "hmx_api_metrics.inc"
+#include "hmx_api_silhouette.inc"

@@ -349,6 +349,20 @@ void l_knn(const Launch& L, const KnnDev& P);
 void l_lisi(const Launch& L, const int* idx, const float* dist, long long Nq, int m, const int* labels, long long N, int ncols, double perplexity,
             double* out);
 
+// ---- silhouette widths (hmx_silhouette.hip) ----------------------------------------------------------------------------------------------
+constexpr int SIL_FLUSH = 32;              // 16-row tiles a lane adds in fp32 before its sums are reduced (4 more additions) into fp64
+struct SilTile { int group, label, rows, count; };   // a 16-row tile of the sorted layout: dense group index, label code, real rows (1..16) | last tile of its segment << 8, cells of the segment
+struct SilDev {
+  const float* X; const float* xn; long long Np;     // rows sorted by (group, label), every segment padded to 16 rows: [Np][zs] (pads 0), squared norms
+  const int* src;                                    // [Np] the cell a sorted row came from, -1: padding
+  const SilTile* tile;                               // [Np / 16]
+  const int* grange;                                 // [groups present][2] the tiles [first, end) of a group
+  int zs, NG;                                        // row stride, PC groups of 16
+  double* s; double* a; double* b;                   // [N] results in the order the cells were given in
+};
+void l_sil_gather(const Launch& L, const float* rows, const float* nrm, const int* src, long long Np, int zs, float* dst, float* dnrm);
+void l_silhouette(const Launch& L, const SilDev& P);
+
 // ---- reference arithmetic: restarted sequential fp32 sums (hmx_seq.hip)------------------------------------------------------------
 struct SeqSeg { int off; int cnt; };       // a segment of a chain: cells list[off .. off + cnt) (or the cells off .. off + cnt - 1 themselves)
 struct SeqChain { int seg0; int nseg; };   // the segments of one chain, in chain order

@@ -292,6 +292,13 @@ class Harmony(object):
         from .metrics import harmony_lisi
         return harmony_lisi(self, meta_data, label_colnames, perplexity)
 
+    def silhouette(self, meta_data, label_col, group_col=None, return_ab=False):
+        """Silhouette widths (silhouette.silhouette_samples) of the handle's current Z_corr over the column `label_col` of meta_data, within the
+        levels of `group_col` when one is named; one label per cell in the order the cells were given in.  Returns s, or (s, a, b).  Z_corr
+        is read where it lives in HBM; no host round trip."""
+        from .silhouette import harmony_silhouette
+        return harmony_silhouette(self, meta_data, label_col, group_col, return_ab)
+
     def getZorig(self):
         return self._get("Z_orig", (int(self.d), int(self._scalar("N_local"))))
 

@@ -105,6 +105,20 @@ if lb:
                                 lb["bound_ms_gemm_fp32_mfma"] / lb["median_ms_knn"], kt or "not collected"))
 else:
     vals["LISI_MEASURED"] = "**Not measured yet**: `profiles/r7_lisi_bench.json` (written by `tools/lisi_bench.py` on an MI355X) is not in the tree."
+sb = line(TAG + "_silhouette_bench.json")      # tools/silhouette_bench.py
+if sb:
+    rows = []
+    for r in sb["sizes"]:
+        lab, bat, kn = r["label"], r["batch_within_label"], r["knn"]
+        rows.append("N = %s: label silhouette %.0f ms (GEMM bound %.0f ms, %.2f of the fp32 matrix-core peak; square roots %.0f ms), batch silhouette within the "
+                    "cell types %.0f ms (%.3f N² pairs, GEMM bound %.1f ms), `hmx_knn` with k = %d %.0f ms — the label silhouette takes %.2f of the kNN's time"
+                    % ("{:,}".format(r["cells"]).replace(",", " "), lab["ms_median"], lab["bound_ms_gemm_fp32_mfma"], lab["bound_ms_gemm_fp32_mfma"] / lab["ms_median"],
+                       lab["bound_ms_sqrt"], bat["ms_median"], bat["pairs"] / float(r["cells"]) ** 2, bat["bound_ms_gemm_fp32_mfma"], sb["knn_k"], kn["ms_median"],
+                       r["label_over_knn"]))
+    vals["SIL_MEASURED"] = ("**Measured** (`profiles/%s_silhouette_bench.json`, one MI355X, median of %d calls, host time around the call with the sort and the "
+                            "copies in it): %s." % (TAG, sb["repeats"], "; ".join(rows)))
+else:
+    vals["SIL_MEASURED"] = ("**Not measured yet**: `profiles/%s_silhouette_bench.json` (written by `tools/silhouette_bench.py` on an MI355X) is not in the tree." % TAG)
 parts = sorted(f for f in os.listdir(os.path.join(ROOT, "docs", "design_parts")) if f.endswith(".md"))
 out = io.StringIO()
 for f in parts:

@@ -5,7 +5,7 @@ object) over the C ABI in include/harmony_mi355x.h.  All numerics run in hand-wr
 (harmony_amd/csrc); there is no CPU fallback.
 """
 from .harmony_obj import Harmony, HarmonyError
-from .mapping import HarmonyReference, map_query
+from .mapping import HarmonyReference, map_query, mapping_confidence
 from .metrics import compute_lisi, knn, knn_predict, lisi_from_knn
 from .options import harmony_options
 from .silhouette import silhouette_batch, silhouette_label, silhouette_samples
@@ -13,5 +13,5 @@ from .ui import RunHarmony, prepare_setup_args
 from .utils import harmonize
 
 __all__ = ["RunHarmony", "harmony_options", "Harmony", "HarmonyError", "harmonize", "prepare_setup_args", "map_query",
-           "HarmonyReference", "knn", "compute_lisi", "lisi_from_knn", "knn_predict",
+           "HarmonyReference", "mapping_confidence", "knn", "compute_lisi", "lisi_from_knn", "knn_predict",
            "silhouette_samples", "silhouette_label", "silhouette_batch"]

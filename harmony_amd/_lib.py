@@ -78,6 +78,12 @@ SILHOUETTE_SIGNATURES = {
     "hmx_silhouette": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32, _ip, C.c_int32, _ip, C.c_int32, _dp, _dp, _dp]),
 }
 
+# the symbols include/harmony_mi355x_confidence.h declares (reference moments, mapping confidence)
+CONFIDENCE_SIGNATURES = {
+    "hmx_reference_moments": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp]),
+    "hmx_mapping_confidence": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp, C.c_int32, C.c_int32, C.c_double, _dp, _fp]),
+}
+
 _lib = None
 
 
@@ -95,7 +101,8 @@ def load():
             "libharmony_mi355x.so is not built (%s). Run `python -m harmony_amd.build`; "
             "harmony_amd has no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(METRICS_SIGNATURES.items()) + list(SILHOUETTE_SIGNATURES.items()):
+    for name, (res, args) in (list(SIGNATURES.items()) + list(METRICS_SIGNATURES.items()) + list(SILHOUETTE_SIGNATURES.items())
+                              + list(CONFIDENCE_SIGNATURES.items())):
         fn = getattr(lib, name)  # AttributeError if the ABI and the header drift apart
         fn.restype = res
         fn.argtypes = args

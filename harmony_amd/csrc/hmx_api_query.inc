@@ -15,9 +15,10 @@ static void query_chunks(const std::vector<int>& start, int64_t n, int target, s
   qchunk[Q] = (int)chunks.size();
 }
 
-// statistics pass + fixed-order fold: out[q][k][0..d) = sum over combination q's cells of R_k z, out[q][k][d] = sum R_k (fp64, on the host)
+// statistics pass + fixed-order fold: out[q][k][0..d) = sum over combination q's cells of R_k z, out[q][k][d] = sum R_k (fp64, on the host);
+// summary 2 (pass A of the reference moments, hmx_api_confidence.inc): one more entry per cluster, out[q][k][d + 1] = sum R_k^2
 static int query_sums(hmx_ctx* ctx, QueryDev Q, int summary, const std::vector<Item>& chunks, const std::vector<int>& qchunk, std::vector<double>& out) {
-  const int total = Q.K * (Q.d + 1), nq = (int)qchunk.size() - 1;
+  const int total = Q.K * query_stats_width(Q.d, summary), nq = (int)qchunk.size() - 1;
   const int nsl = (total + QUERY_SLICE - 1) / QUERY_SLICE;
   Q.slice = (total + nsl - 1) / nsl;
   Q.nchunks = (int)chunks.size();

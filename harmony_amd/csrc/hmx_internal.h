@@ -329,9 +329,35 @@ struct QueryDev {
   float* out; float* Rout;     // [n][zs] Z_corr rows / [n][K] R rows (either may be nullptr)
 };
 constexpr int QUERY_SLICE = 6144;          // 48 KB of fp64 accumulators per workgroup
+// statistics entries per cluster: d sums of R z, sum R and (summary 2: pass A of the reference moments) sum R^2
+__host__ __device__ constexpr int query_stats_width(int d, int summary) { return d + (summary == 2 ? 2 : 1); }
 void l_query_stats(const Launch& L, const QueryDev& Q, int summary);
 void l_query_fold(const Launch& L, const double* part, const int* qchunk, int nq, int total, double* out);
 void l_query_apply(const Launch& L, const QueryDev& Q);
+
+// ---- mapping confidence: reference moments and per-cell Mahalanobis score (hmx_confidence.hip) ------------------------------------------
+constexpr int CONF_BLOCK = 64;             // cells staged through LDS at a time by the moments pass (four 16-cell tiles)
+constexpr int CONF_FLUSH = 8;              // 16-cell tiles a product is added in fp32 before the sums go to fp64: 128 additions (the rule is <= 256)
+constexpr int CONF_TILES = 4;              // 16-cell tiles (one per wave) that share one fetch of a cluster's whitening matrix
+// pass B of the moments: per (chunk, cluster) the centred second-moment tiles of the upper triangle and the centred first moment.
+// Pair p = (a, b), a <= b, row-major over the upper triangle of the NG x NG grid of 16 x 16 tiles; a slot of E = 256 npairs + 16 NG doubles:
+// [p][lane = 16 g + r][i] = sum R y_(16 a + 4 g + i) y_(16 b + r), then [16 t + r] = sum R y_(16 t + r), y = z - c_k
+struct ConfMomDev {
+  const float* Z; const float* R;          // [n][zs] the chosen rows, [n][K]
+  const float* c;                          // [K][zs] centres fl32(mu_k) of pass A (pads 0)
+  const Item* chunks; int nchunks;         // contiguous cells, multiples of CONF_BLOCK but the last
+  int K, zs, NG, npairs, E;
+  double* part;                            // [nchunks][K][E]
+};
+void l_conf_moments(const Launch& L, const ConfMomDev& P);
+struct ConfDev {
+  QueryDev Q;                              // the mapping's own assignment state: Q.Z = the query's Z_orig rows, yhat, sig2, chunks
+  const float* Zs;                         // [n][zs] the rows the distances are measured on (Z_orig or Z_corr of the query)
+  const float* U; const float* mu;         // [K][zs][zs] U_k = L_k^-1 (lower triangular, 0 above the diagonal and in the pads), [K][zs] means
+  const int* perm;                         // [n] internal -> given order
+  double* score; float* dist;              // [n], [n][K] (or nullptr), in the order the cells were given in
+};
+void l_conf_score(const Launch& L, const ConfDev& P);
 
 // ---- integration metrics: exact kNN and LISI (hmx_knn.hip) ------------------------------------------------------------------------------
 constexpr int KNN_QROWS = 64;              // query rows per workgroup (16 per wave)

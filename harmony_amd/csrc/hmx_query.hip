@@ -9,84 +9,11 @@
 //   k_query_apply     recomputes R of the tile the same way and writes Z_corr = Z - sum_k R_k Wq[q][k][:] (or, on request, R).
 // k_query_stats<1> is the same accumulation with R read from a fitted handle's rows: Nr = sum R, Cref = sum R Z_corr.
 #include "hmx_internal.h"
+#include "hmx_query_tile.h"      // q_load_tile / q_assign: the tile's rows and its soft assignment
 
 namespace hmx {
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int QT = 16;          // cells per tile
-constexpr int QZS = 128;        // largest row stride (d <= 128)
-constexpr int QKP = 256;        // largest K
-
-__device__ __forceinline__ float qwmax(float v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v = fmaxf(v, __shfl_xor(v, m, 64));
-  return v;
-}
-__device__ __forceinline__ float qwsum(float v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
-
-// rows s .. s + cnt - 1 of Z into zt (pads and missing cells 0) and their inverse norms
-__device__ __forceinline__ void q_load_tile(const QueryDev& Q, const float* __restrict__ Z, int s, int cnt, float (*zt)[QZS], float* inv) {
-  const int zs = Q.zs;
-  for (int i = threadIdx.x; i < QT * zs; i += blockDim.x) {
-    const int c = i / zs, j = i - c * zs;
-    zt[c][j] = c < cnt ? Z[(size_t)(s + c) * zs + j] : 0.f;
-  }
-  __syncthreads();
-  const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
-  for (int c = w; c < QT; c += blockDim.x >> 6) {
-    float ss = 0.f;
-    for (int j = l; j < zs; j += 64) ss += zt[c][j] * zt[c][j];
-    ss = qwsum(ss);
-    if (l == 0) inv[c] = ss > 0.f ? 1.0f / sqrtf(ss) : 0.f;
-  }
-  __syncthreads();
-}
-
-// R of the tile into lg[c][k] (0 for missing cells): dot of the normalised row with every normalised centroid on the matrix cores
-// (wave w takes the cluster tiles w, w + 4, ...), logits (dot - 1) * 2 / sigma_k, column maximum subtracted, exp, normalised.
-__device__ __forceinline__ void q_assign(const QueryDev& Q, int cnt, float (*zt)[QZS], const float* inv, float (*lg)[QKP]) {
-  const int w = threadIdx.x >> 6, l = threadIdx.x & 63, nw = blockDim.x >> 6;
-  const int r = l & 15, g = l >> 4;
-  const int nct = Q.KP16 >> 4;
-  for (int ct = w; ct < nct; ct += nw) {
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    const float* yrow = Q.yhat + (size_t)(16 * ct + r) * Q.zs;
-    const float iv = inv[r];
-    for (int j0 = 0; j0 < Q.zs; j0 += 4) {
-      const float a = zt[r][j0 + g] * iv;             // A[cell r][step g]
-      const float b = yrow[j0 + g];                   // B[step g][cluster 16 ct + r]
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc, 0, 0, 0);
-    }
-    const int k = 16 * ct + r;
-    if (k < Q.K) {
-      const float s2 = Q.sig2[k];
-#pragma unroll
-      for (int i = 0; i < 4; i++) lg[4 * g + i][k] = (acc[i] - 1.0f) * s2;     // D[cell 4 g + i][cluster k]
-    }
-  }
-  __syncthreads();
-  for (int c = w; c < QT; c += nw) {
-    if (c >= cnt) {
-      for (int k = l; k < Q.K; k += 64) lg[c][k] = 0.f;
-      continue;
-    }
-    float m = -INFINITY;
-    for (int k = l; k < Q.K; k += 64) m = fmaxf(m, lg[c][k]);
-    m = qwmax(m);
-    float s = 0.f;
-    for (int k = l; k < Q.K; k += 64) { const float e = expf(lg[c][k] - m); lg[c][k] = e; s += e; }
-    s = qwsum(s);
-    const float is = 1.0f / s;
-    for (int k = l; k < Q.K; k += 64) lg[c][k] *= is;
-  }
-  __syncthreads();
-}
-
-// SUMMARY = 0: query statistics (R from the assignment, z = the query rows); 1: reference summary (R and z = the fitted handle's rows).
+// SUMMARY = 0: query statistics (R from the assignment, z = the query rows); 1: reference summary (R and z = the fitted handle's rows);
+// 2: the summary with one more column, [k][d + 1] = sum R^2 (pass A of the reference moments, hmx_confidence.hip).
 // Workgroup (x, y) = (chunk, slice of the K (d + 1) entries [k][0..d) = sum R z, [k][d] = sum R); fp64 accumulators in LDS.
 template <int SUMMARY>
 __global__ __launch_bounds__(256) void k_query_stats(QueryDev Q) {
@@ -94,7 +21,7 @@ __global__ __launch_bounds__(256) void k_query_stats(QueryDev Q) {
   __shared__ float zt[QT][QZS];
   __shared__ float lg[QT][QKP];
   __shared__ float inv[QT];
-  const int W1 = Q.d + 1, total = Q.K * W1;
+  const int W1 = query_stats_width(Q.d, SUMMARY), total = Q.K * W1;
   const int e0 = blockIdx.y * Q.slice, e1 = min(total, e0 + Q.slice);
   for (int e = e0 + threadIdx.x; e < e1; e += blockDim.x) qacc[e - e0] = 0.0;
   const Item it = Q.chunks[blockIdx.x];
@@ -118,9 +45,12 @@ __global__ __launch_bounds__(256) void k_query_stats(QueryDev Q) {
       if (j < Q.d) {
 #pragma unroll
         for (int c = 0; c < QT; c++) t += lg[c][k] * zt[c][j];
-      } else {
+      } else if (j == Q.d) {
 #pragma unroll
         for (int c = 0; c < QT; c++) t += lg[c][k];
+      } else {
+#pragma unroll
+        for (int c = 0; c < QT; c++) t += lg[c][k] * lg[c][k];
       }
       qacc[e - e0] += (double)t;
     }
@@ -180,9 +110,10 @@ __global__ __launch_bounds__(256) void k_query_apply(QueryDev Q) {
 size_t query_stats_lds(const QueryDev& Q) { return (size_t)Q.slice * sizeof(double); }
 
 void l_query_stats(const Launch& L, const QueryDev& Q, int summary) {
-  const int total = Q.K * (Q.d + 1), nsl = (total + Q.slice - 1) / Q.slice;
+  const int total = Q.K * query_stats_width(Q.d, summary), nsl = (total + Q.slice - 1) / Q.slice;
   const dim3 grid((unsigned)Q.nchunks, (unsigned)nsl);
-  if (summary) hipLaunchKernelGGL(k_query_stats<1>, grid, dim3(256), query_stats_lds(Q), L.stream, Q);
+  if (summary == 2) hipLaunchKernelGGL(k_query_stats<2>, grid, dim3(256), query_stats_lds(Q), L.stream, Q);
+  else if (summary) hipLaunchKernelGGL(k_query_stats<1>, grid, dim3(256), query_stats_lds(Q), L.stream, Q);
   else hipLaunchKernelGGL(k_query_stats<0>, grid, dim3(256), query_stats_lds(Q), L.stream, Q);
 }
 void l_query_fold(const Launch& L, const double* part, const int* qchunk, int nq, int total, double* out) {

@@ -201,12 +201,38 @@ class Harmony(object):
             self.warnings.append(w)
             warnings.warn(w)
 
-    def reference_summary(self):
-        """The fitted state a query is mapped onto (hmx_get "ref_Nr" / "ref_C" / "sigma"): a HarmonyReference.  Collective on a sharded
-        handle: every rank calls it and gets the global summary."""
-        from .mapping import HarmonyReference
+    def reference_summary(self, moments=None):
+        """The fitted state a query is mapped onto (hmx_get "ref_Nr" / "ref_C" / "sigma"): a HarmonyReference.  moments = "orig" | "corr":
+        also the soft clusters' means and covariances over the Z_orig / Z_corr rows (hmx_reference_moments), which mapping_confidence()
+        needs.  Collective on a sharded handle: every rank calls it and gets the global summary."""
+        from .mapping import SPACES, HarmonyReference
+        if moments is not None and moments not in SPACES:
+            raise ValueError("reference_summary: moments must be None, 'orig' or 'corr'")
         K, d = int(self.K), int(self.d)
-        return HarmonyReference(self._get("ref_Nr"), self._get("ref_C", (K, d)), self._get("sigma"))
+        Nr, Cr, sigma = self._get("ref_Nr"), self._get("ref_C", (K, d)), self._get("sigma")
+        if moments is None:
+            return HarmonyReference(Nr, Cr, sigma)
+        mean = np.empty((K, d), dtype=np.float64, order="F")
+        cov = np.empty((K, d, d), dtype=np.float64)
+        self._check(self._lib.hmx_reference_moments(self._h, SPACES.index(moments), _dptr(mean), _dptr(cov)), "reference_moments")
+        return HarmonyReference(Nr, Cr, sigma, mean=mean, cov=cov, space=moments)
+
+    def mapping_confidence(self, reference, ridge=0.0, return_dist=False):
+        """Per-cell mapping confidence of this mapped query against the moments of `reference` (mapping.mapping_confidence)."""
+        from .mapping import mapping_confidence
+        return mapping_confidence(self, reference, ridge, return_dist)
+
+    def _mapping_confidence(self, mean, cov, space, ridge, return_dist):
+        mean = np.asfortranarray(mean, dtype=np.float64)
+        cov = np.ascontiguousarray(cov, dtype=np.float64)
+        K, d = mean.shape
+        n = int(self._scalar("N_local"))
+        score = np.empty(n, dtype=np.float64)
+        dist = np.empty((n, K), dtype=np.float32) if return_dist else None
+        st = self._lib.hmx_mapping_confidence(self._h, int(space), _dptr(mean), _dptr(cov), int(K), int(d), float(ridge), _dptr(score),
+                                              None if dist is None else dist.ctypes.data_as(C.POINTER(C.c_float)))
+        self._check(st, "mapping_confidence")
+        return (score, dist) if return_dist else score
 
     def map_query(self, Zq, Phi, B_vec, lambda_vec, alpha, batch_proportion_cutoff, reference):
         """hmx_map_query on this (fresh) handle.  Zq: d x Nq numpy array (float64 or float32) or a device buffer (d, Nq, dtype,

@@ -13,12 +13,15 @@ from .ui import _columns, as_factor, build_phi, lambda_vector
 from .utils import _message
 
 FORMAT = "harmony_amd.reference/1"
+FORMAT_MOMENTS = "harmony_amd.reference/2"      # the same arrays plus the clusters' moments (mean, cov, space)
+SPACES = ("orig", "corr")                       # HMX_SPACE_ORIG / HMX_SPACE_CORR of include/harmony_mi355x_confidence.h
 
 
 class HarmonyReference(object):
-    """The summary of a fitted reference: Nr (K,), C (K x d), sigma (K,)."""
+    """The summary of a fitted reference: Nr (K,), C (K x d), sigma (K,); optionally the soft clusters' moments that mapping_confidence()
+    measures a query against: mean (K x d), cov (K x d x d) and the space ("orig" | "corr") they were taken in."""
 
-    def __init__(self, Nr, C, sigma):
+    def __init__(self, Nr, C, sigma, mean=None, cov=None, space=None):
         self.Nr = np.asarray(Nr, dtype=np.float64).reshape(-1)
         self.C = np.asarray(C, dtype=np.float64)
         self.sigma = np.asarray(sigma, dtype=np.float64).reshape(-1)
@@ -26,6 +29,21 @@ class HarmonyReference(object):
         if self.C.ndim != 2 or self.C.shape[0] != K or self.sigma.size != K:
             raise ValueError("HarmonyReference: Nr (K), C (K x d) and sigma (K) do not agree: %s %s %s"
                              % (self.Nr.shape, self.C.shape, self.sigma.shape))
+        self.mean = self.cov = self.space = None
+        if mean is not None or cov is not None:
+            if mean is None or cov is None:
+                raise ValueError("HarmonyReference: mean and cov come together")
+            self.mean = np.asarray(mean, dtype=np.float64)
+            self.cov = np.asarray(cov, dtype=np.float64)
+            self.space = "orig" if space is None else str(space)
+            d = self.C.shape[1]
+            if self.mean.shape != (K, d) or self.cov.shape != (K, d, d):
+                raise ValueError("HarmonyReference: mean must be K x d = %s and cov K x d x d, got %s and %s"
+                                 % ((K, d), self.mean.shape, self.cov.shape))
+            if self.space not in SPACES:
+                raise ValueError("HarmonyReference: space must be 'orig' or 'corr', got %r" % (space,))
+        elif space is not None:
+            raise ValueError("HarmonyReference: space without mean and cov")
 
     K = property(lambda s: int(s.Nr.size))
     d = property(lambda s: int(s.C.shape[1]))
@@ -33,14 +51,21 @@ class HarmonyReference(object):
     def save(self, path):
         """.npz of plain arrays plus a format tag"""
         with open(path, "wb") as f:
-            np.savez(f, format=np.array(FORMAT), Nr=self.Nr, C=self.C, sigma=self.sigma)
+            if self.mean is None:
+                np.savez(f, format=np.array(FORMAT), Nr=self.Nr, C=self.C, sigma=self.sigma)
+            else:
+                np.savez(f, format=np.array(FORMAT_MOMENTS), Nr=self.Nr, C=self.C, sigma=self.sigma, mean=self.mean, cov=self.cov,
+                         space=np.array(self.space))
 
     @classmethod
     def load(cls, path):
         with np.load(path, allow_pickle=False) as z:
-            if "format" not in z.files or str(z["format"]) != FORMAT:
-                raise ValueError("%s is not a saved HarmonyReference (%s)" % (path, FORMAT))
-            return cls(z["Nr"], z["C"], z["sigma"])
+            tag = str(z["format"]) if "format" in z.files else None
+            if tag not in (FORMAT, FORMAT_MOMENTS):
+                raise ValueError("%s is not a saved HarmonyReference (%s or %s)" % (path, FORMAT, FORMAT_MOMENTS))
+            if tag == FORMAT:
+                return cls(z["Nr"], z["C"], z["sigma"])
+            return cls(z["Nr"], z["C"], z["sigma"], mean=z["mean"], cov=z["cov"], space=str(z["space"]))
 
 
 def prepare_query_args(data_mat, meta_data, reference, vars_use=None, lambda_=None, options=None, verbose=False):
@@ -106,3 +131,23 @@ def map_query(data_mat, meta_data, reference, vars_use=None, lambda_=None, optio
     if return_object:
         return obj
     return obj.getZcorr().T
+
+
+def mapping_confidence(obj, reference, ridge=0.0, return_dist=False):
+    """Per-cell mapping confidence of a mapped query (Symphony's calcPerCellMappingMetric): the R-weighted Mahalanobis distance of every query
+    cell to the reference's soft clusters, score[i] = sum_k R[k,i] || U_k (z_i - mean_k) ||, U_k the inverse Cholesky factor of cov_k + ridge I.
+    `obj`: the Harmony object of map_query(..., return_object=True); `reference`: a HarmonyReference with moments
+    (``Harmony.reference_summary(moments="orig")``).  z_i is the query's Z_orig row for moments taken in "orig", its Z_corr row for "corr".
+    Returns score (Nq,), or (score, dist Nq x K float32), in the order the cells were given in.  Large scores: cells the reference does not
+    explain.  All numerics run in libharmony_mi355x.so (hmx_mapping_confidence)."""
+    if getattr(reference, "mean", None) is None or getattr(reference, "cov", None) is None:
+        raise ValueError("mapping_confidence: the reference carries no moments; build it with Harmony.reference_summary(moments='orig')")
+    ridge = float(ridge)
+    if not (ridge >= 0) or not np.isfinite(ridge):
+        raise ValueError("mapping_confidence: ridge must be finite and non-negative")
+    if not isinstance(obj, Harmony):
+        raise ValueError("mapping_confidence: obj must be the Harmony object of map_query(..., return_object=True)")
+    K, d = int(obj.K), int(obj.d)
+    if (reference.K, reference.d) != (K, d):
+        raise ValueError("mapping_confidence: the reference has K = %d, d = %d, the mapped query K = %d, d = %d" % (reference.K, reference.d, K, d))
+    return obj._mapping_confidence(reference.mean, reference.cov, SPACES.index(reference.space), ridge, return_dist)

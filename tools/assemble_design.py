@@ -119,6 +119,17 @@ if sb:
                             "copies in it): %s." % (TAG, sb["repeats"], "; ".join(rows)))
 else:
     vals["SIL_MEASURED"] = ("**Not measured yet**: `profiles/%s_silhouette_bench.json` (written by `tools/silhouette_bench.py` on an MI355X) is not in the tree." % TAG)
+cb = line(TAG + "_confidence_bench.json")      # tools/confidence_bench.py
+if cb:
+    rm, so, sd = cb["reference_moments"], cb["mapping_confidence_score_only"], cb["mapping_confidence_score_and_dist"]
+    vals["CONF_MEASURED"] = ("**Measured** (`profiles/%s_confidence_bench.json`, one MI355X, %s cells x %d PCs, K = %d, median of %d calls, host time around the "
+                             "call): `reference_summary(moments=\"orig\")` %.1f ms, of which `hmx_reference_moments` %.1f ms (pass B's MFMA bound %.1f ms; the rest is the plain summary), "
+                             "the confidence of the mapped query %.1f ms for the score alone "
+                             "(MFMA bound %.1f ms, the host's Cholesky factors and the copies in it) and %.1f ms with the distance matrix."
+                             % (TAG, "{:,}".format(cb["cells"]).replace(",", " "), cb["d"], cb["K"], cb["repeats"], rm["ms_median"], rm["timer_ms_median"], rm["bound_ms_fp32_mfma"],
+                                so["ms_median"], so["bound_ms_fp32_mfma"], sd["ms_median"]))
+else:
+    vals["CONF_MEASURED"] = ("**Not measured yet**: `profiles/%s_confidence_bench.json` (written by `tools/confidence_bench.py` on an MI355X) is not in the tree." % TAG)
 parts = sorted(f for f in os.listdir(os.path.join(ROOT, "docs", "design_parts")) if f.endswith(".md"))
 out = io.StringIO()
 for f in parts:

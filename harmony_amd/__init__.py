@@ -8,10 +8,11 @@ from .harmony_obj import Harmony, HarmonyError
 from .mapping import HarmonyReference, map_query, mapping_confidence
 from .metrics import compute_lisi, knn, knn_predict, lisi_from_knn
 from .options import harmony_options
+from .project import HarmonyLoadings, map_query_counts, project_query
 from .silhouette import silhouette_batch, silhouette_label, silhouette_samples
 from .ui import RunHarmony, prepare_setup_args
 from .utils import harmonize
 
 __all__ = ["RunHarmony", "harmony_options", "Harmony", "HarmonyError", "harmonize", "prepare_setup_args", "map_query",
            "HarmonyReference", "mapping_confidence", "knn", "compute_lisi", "lisi_from_knn", "knn_predict",
-           "silhouette_samples", "silhouette_label", "silhouette_batch"]
+           "silhouette_samples", "silhouette_label", "silhouette_batch", "HarmonyLoadings", "project_query", "map_query_counts"]

@@ -84,6 +84,12 @@ CONFIDENCE_SIGNATURES = {
     "hmx_mapping_confidence": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp, C.c_int32, C.c_int32, C.c_double, _dp, _fp]),
 }
 
+# the symbol include/harmony_mi355x_project.h declares (raw counts -> the reference's PC space)
+PROJECT_SIGNATURES = {
+    "hmx_project_counts": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, _ip,
+                                     _dp, _dp, _dp, C.c_int32, C.c_int32, C.c_double, C.c_double, _dp, C.c_void_p, C.c_int32]),
+}
+
 _lib = None
 
 
@@ -102,7 +108,7 @@ def load():
             "harmony_amd has no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in (list(SIGNATURES.items()) + list(METRICS_SIGNATURES.items()) + list(SILHOUETTE_SIGNATURES.items())
-                              + list(CONFIDENCE_SIGNATURES.items())):
+                              + list(CONFIDENCE_SIGNATURES.items()) + list(PROJECT_SIGNATURES.items())):
         fn = getattr(lib, name)  # AttributeError if the ABI and the header drift apart
         fn.restype = res
         fn.argtypes = args

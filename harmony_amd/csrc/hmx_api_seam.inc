@@ -255,6 +255,8 @@ struct hmx_ctx {
   bool shuf_inv = false; int2* posr[4] = {}; int* shuf_partcnt[4] = {}; int* shuf_binacc[4] = {}; int64_t injected_round = -1;   // (injected_round: the round whose order the host provided -- its D.blk came with it)
   // ---- query mapping (hmx_map_query): a handle that mapped a query serves Z_corr / Z_orig / R and nothing else
   bool query_done = false;
+  // ---- count projection (hmx_project_counts): the lab field "project_slab_bytes" (0: the default cap) and the slabs the last host-resident call ran
+  int64_t project_slab_bytes = 0, project_slabs = 0;
   QueryDev qd{};            // the query's device tables (rows in D.Zo / D.Zc, internal order in D.perm / D.invperm)
   std::string err, warn, warn_ret;
 };

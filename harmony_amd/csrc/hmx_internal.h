@@ -359,6 +359,25 @@ struct ConfDev {
 };
 void l_conf_score(const Launch& L, const ConfDev& P);
 
+// ---- projection of raw query counts into the reference's PC space (hmx_project.hip) -----------------------------------------------------
+constexpr int PROJ_WAVES = 4;              // waves (= cells in flight) per workgroup
+constexpr int PROJ_SWEEPS = 4;             // sweeps of 64 stored entries whose loads a wave issues together
+enum { PROJ_BAD_INDPTR = 1, PROJ_BAD_COLUMN = 2, PROJ_BAD_NEGATIVE = 4, PROJ_BAD_NONFINITE = 8 };      // bits of the flag word, in the order they are reported
+struct ProjDev {
+  const long long* indptr; long long base, nnz;      // [nrows + 1] row offsets of this launch's rows; entry e of indices / data is offset - base, valid in [0, nnz)
+  const int* indices; const void* data; int f64;     // [nnz] columns, values (fp32, or fp64 when f64)
+  const int* slot;                                   // [G_all] row of the reference's tables or -1
+  const float* U; const float* inv_sd; const float* cap;      // [G][64 ceil(d / 64)] loadings (pads 0), [G] 1 / sd, [G] mean + clip sd (+inf: no clip)
+  const double* b;                                   // [d] sum over the genes present of (-mean / sd) U[j,:]
+  const double* totals;                              // [row0 + nrows] library sizes, or nullptr: the row sums
+  double scale;
+  long long nrows, row0;                             // rows of this launch, the first one's index in totals / out
+  int G_all, G, d;
+  float* out;                                        // [Nq][d]
+  unsigned* flag;                                    // |= PROJ_BAD_*
+};
+void l_project(const Launch& L, const ProjDev& P, hipStream_t stream);
+
 // ---- integration metrics: exact kNN and LISI (hmx_knn.hip) ------------------------------------------------------------------------------
 constexpr int KNN_QROWS = 64;              // query rows per workgroup (16 per wave)
 constexpr int KNN_SLAB = 64;               // data rows staged per step

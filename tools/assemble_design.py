@@ -130,6 +130,18 @@ if cb:
                                 so["ms_median"], so["bound_ms_fp32_mfma"], sd["ms_median"]))
 else:
     vals["CONF_MEASURED"] = ("**Not measured yet**: `profiles/%s_confidence_bench.json` (written by `tools/confidence_bench.py` on an MI355X) is not in the tree." % TAG)
+pb = line(TAG + "_project_bench.json")      # tools/project_bench.py
+if pb:
+    dv, ho = pb["device_resident"], pb["host_resident"]
+    vals["PROJECT_MEASURED"] = ("**Measured** (`profiles/%s_project_bench.json`, one MI355X, %s cells x %d genes, %.0f stored counts per cell, G = %d, d = %d, PCs left in "
+                                "HBM, median of %d calls by the library's timer): device-resident %.1f ms (two sweeps from HBM would take %.1f ms, one %.1f ms: the call moves "
+                                "%.2f TB/s counted as one sweep), host-resident %.0f ms in %d slabs, %.1f GB/s across PCIe with the host's validation pass in it; "
+                                "the two give the same bits: %s."
+                                % (TAG, "{:,}".format(pb["cells"]).replace(",", " "), pb["G_all"], pb["nnz_per_cell"], pb["G"], pb["d"], pb["repeats"], dv["timer_ms_median"],
+                                   dv["bound_ms_two_sweeps_from_hbm"], dv["bound_ms_one_sweep_from_hbm"], dv["bytes_per_s_of_one_sweep"] / 1e12, ho["timer_ms_median"],
+                                   ho["slabs"], ho["bytes_per_s"] / 1e9, "yes" if pb["host_equals_device_bits"] else "NO"))
+else:
+    vals["PROJECT_MEASURED"] = ("**Not measured yet**: `profiles/%s_project_bench.json` (written by `tools/project_bench.py` on an MI355X) is not in the tree." % TAG)
 parts = sorted(f for f in os.listdir(os.path.join(ROOT, "docs", "design_parts")) if f.endswith(".md"))
 out = io.StringIO()
 for f in parts:

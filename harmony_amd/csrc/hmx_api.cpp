@@ -353,6 +353,7 @@ int hmx_moe_correct_ridge(hmx_ctx* ctx) {  // src/harmony.cpp:345-638
 }
 
 #include "hmx_api_diag.inc"
+#include "hmx_api_call.inc"
 #include "hmx_api_metrics.inc"
 #include "hmx_api_silhouette.inc"
 #include "hmx_api_confidence.inc"

@@ -1,7 +1,7 @@
-// hmx_api_confidence.inc -- part of hmx_api.cpp (included there, ONE translation unit, behind hmx_api_metrics.inc whose MetricBufs it uses
-// and hmx_api_query.inc whose query_chunks / query_sums run pass A): hmx_reference_moments and hmx_mapping_confidence
+// hmx_api_confidence.inc -- part of hmx_api.cpp (included there, ONE translation unit, behind hmx_api_query.inc whose query_chunks /
+// query_sums run pass A): hmx_reference_moments and hmx_mapping_confidence
 // (include/harmony_mi355x_confidence.h; DESIGN "Mapping confidence").  Kernels: hmx_confidence.hip, k_query_stats<2> of hmx_query.hip.
-// The calls keep no state on the handle but the timers: every device buffer lives for one call.
+// The calls keep no state on the handle but the timers: every device buffer lives for one call (hmx_api_call.inc).
 
 namespace {
 
@@ -100,7 +100,7 @@ int hmx_reference_moments(hmx_ctx* ctx, int32_t space, double* mean, double* cov
   const int fold[2] = {0, P.nchunks};
   std::vector<double> M(total);
   {
-    MetricBufs B;
+    CallBufs B;
     float* dc; Item* dch; int* dfold; double* dres;
     HIPCHK(B.get(&dc, c.size())); HIPCHK(B.get(&dch, chunks.size())); HIPCHK(B.get(&dfold, 2));
     HIPCHK(B.get(&P.part, (size_t)P.nchunks * total)); HIPCHK(B.get(&dres, total));
@@ -186,7 +186,7 @@ int hmx_mapping_confidence(hmx_ctx* ctx, int32_t space, const double* mean, cons
     if (bad[k]) return fail(ctx, HMX_ERR_SOLVE, "mapping confidence: cov + ridge I of cluster " + std::to_string(k) + " is not positive definite");
 
   HIPCHK(hipSetDevice(ctx->device));
-  MetricBufs B;
+  CallBufs B;
   ConfDev P{};
   P.Q = ctx->qd; P.Q.out = nullptr; P.Q.Rout = nullptr;
   P.Zs = space == HMX_SPACE_CORR ? D.Zc : D.Zo;

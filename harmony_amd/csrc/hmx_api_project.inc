@@ -1,6 +1,6 @@
-// hmx_api_project.inc -- part of hmx_api.cpp (included there, ONE translation unit, behind hmx_api_metrics.inc whose MetricBufs and
-// metrics_device it uses): hmx_project_counts (include/harmony_mi355x_project.h; DESIGN "Projecting query counts").  Kernel: hmx_project.hip.
-// The call keeps no state on the handle but the timer: every device buffer lives for one call.
+// hmx_api_project.inc -- part of hmx_api.cpp (included there, ONE translation unit): hmx_project_counts
+// (include/harmony_mi355x_project.h; DESIGN "Projecting query counts").  Kernel: hmx_project.hip.
+// The call keeps no state on the handle but the timer: every device buffer lives for one call (hmx_api_call.inc).
 
 namespace {
 
@@ -93,7 +93,7 @@ int hmx_project_counts(hmx_ctx* ctx, int64_t Nq, int32_t G_all, const int64_t* i
     if (v == 1) return fail(ctx, HMX_ERR_ARG, "indptr is not monotone from 0 (row " + std::to_string(where) + ")");
     if (v == 2) return fail(ctx, HMX_ERR_ARG, "a column index is outside [0, G_all) (entry " + std::to_string(where) + ")");
   }
-  CHK(metrics_device(ctx));
+  CHK(call_device(ctx));
 
   // ---- the tables: b in fp64, the rest as the kernel's fp32
   const int zs = (d + 63) / 64 * 64;
@@ -109,7 +109,7 @@ int hmx_project_counts(hmx_ctx* ctx, int64_t Nq, int32_t G_all, const int64_t* i
     }
   }
 
-  MetricBufs B;
+  CallBufs B;
   ProjDev P{};
   int* dslot; float* dU; float* dinv; float* dcap; double* db; double* dtot = nullptr; unsigned* dflag; float* dout;
   HIPCHK(B.get(&dslot, (size_t)G_all)); HIPCHK(B.get(&dU, U32.size())); HIPCHK(B.get(&dinv, (size_t)G)); HIPCHK(B.get(&dcap, (size_t)G));

@@ -1,6 +1,6 @@
-// hmx_api_silhouette.inc -- part of hmx_api.cpp (included there, ONE translation unit, behind hmx_api_metrics.inc whose MetricBufs,
-// metrics_device, metrics_rows and checks it uses): hmx_silhouette (include/harmony_mi355x_silhouette.h; DESIGN "Silhouette widths").
-// Kernels: hmx_silhouette.hip.  The call keeps no state on the handle but the timer: every device buffer lives for one call.
+// hmx_api_silhouette.inc -- part of hmx_api.cpp (included there, ONE translation unit): hmx_silhouette
+// (include/harmony_mi355x_silhouette.h; DESIGN "Silhouette widths").  Kernels: hmx_silhouette.hip.  The call keeps no state on the handle
+// but the timer: every device buffer lives for one call (hmx_api_call.inc).
 
 namespace {
 
@@ -60,37 +60,19 @@ int hmx_silhouette(hmx_ctx* ctx, const void* X, int32_t x_dtype, int32_t x_locat
                    double* s, double* a, double* b) {
   if (!ctx) return HMX_ERR_ARG;
   ctx->err.clear();
-  const bool own = X == nullptr;            // the handle's current Z_corr
-  if (own) {
-    if (!(ctx->ran_setup || ctx->query_done)) return fail(ctx, HMX_ERR_STATE, "no embedding on this handle: setup or map_query first, or pass X");
-    if (N != ctx->N) return fail(ctx, HMX_ERR_ARG, "N is not the handle's cell count");
-    d = ctx->d;
-  } else {
-    CHK(check_rows(ctx, X, x_dtype, x_location, "X"));
-  }
-  if (!s) return fail(ctx, HMX_ERR_ARG, "null output");
-  if (N <= 0 || d <= 0) return fail(ctx, HMX_ERR_ARG, "non-positive dimension");
-  if (d > 128) return fail(ctx, HMX_ERR_LIMIT, "supported envelope: d <= 128");
-  if (N > 2000000000ll) return fail(ctx, HMX_ERR_LIMIT, "at most 2e9 rows");
+  CHK(score_args(ctx, X, x_dtype, x_location, N, d, s));      // (X == nullptr: the handle's current Z_corr)
+  CHK(score_limits(ctx, N, d));
   CHK(check_labels(ctx, labels, N, 1, &n_levels));
   if (groups) CHK(check_labels(ctx, groups, N, 1, &n_groups));
-  CHK(metrics_device(ctx));
+  CHK(call_device(ctx));
   const double t0 = now_ms();
   const SilLayout Y = sil_layout(labels, n_levels, groups, n_groups, N);
   if (Y.src.size() > 2000000000ull) return fail(ctx, HMX_ERR_LIMIT, "at most 2e9 rows once every (group, label) segment is padded to 16");
-  MetricBufs B;
+  CallBufs B;
   SilDev P{};
   P.zs = (d + 3) / 4 * 4; P.NG = (P.zs + 15) / 16; P.Np = (long long)Y.src.size();
   float* xr; float* xn;
-  if (own) {
-    CHK(sync_solve_results(ctx));      // (a singular system of the last correction surfaces here, as in hmx_get_matrix)
-    float* dense;                                           // Z_corr in the order the cells were given in
-    HIPCHK(B.get(&dense, (size_t)N * d));
-    l_convert_out(ctx->L, ctx->D.Zc, dense, 1, ctx->D.invperm, ctx->D.n, d, ctx->D.zs); KCHK();
-    CHK(metrics_rows(ctx, B, dense, HMX_F32, HMX_DEVICE, N, d, P.zs, &xr, &xn));
-  } else {
-    CHK(metrics_rows(ctx, B, X, x_dtype, x_location, N, d, P.zs, &xr, &xn));
-  }
+  CHK(score_rows(ctx, B, X, x_dtype, x_location, N, d, P.zs, &xr, &xn));
   int* dsrc; SilTile* dtile; int* dgrange; float* sr; float* sn;
   HIPCHK(B.get(&dsrc, Y.src.size())); HIPCHK(B.get(&dtile, Y.tile.size())); HIPCHK(B.get(&dgrange, Y.grange.size()));
   HIPCHK(B.get(&sr, (size_t)P.Np * P.zs)); HIPCHK(B.get(&sn, (size_t)P.Np));

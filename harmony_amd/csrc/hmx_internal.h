@@ -378,6 +378,14 @@ struct ProjDev {
 };
 void l_project(const Launch& L, const ProjDev& P, hipStream_t stream);
 
+// the sum over the 64 lanes of a wave, in every one of them (xor butterfly: the same order of additions in every lane)
+template <class T>
+__device__ __forceinline__ T wave_sum(T v) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+  return v;
+}
+
 // ---- integration metrics: exact kNN and LISI (hmx_knn.hip) ------------------------------------------------------------------------------
 constexpr int KNN_QROWS = 64;              // query rows per workgroup (16 per wave)
 constexpr int KNN_SLAB = 64;               // data rows staged per step

@@ -10,10 +10,9 @@
 //   k_lisi         one wave per cell: the perplexity search of the neighbour weights and the Simpson index of every label column, fp64.
 // A key is (order-preserving bits of d2) << 32 | data index, so that one 64-bit comparison orders by (d2, index): ties go to the smaller
 // index, keys are unique, and the k smallest of a set do not depend on the order they were offered in -- no atomics, bit-reproducible.
-#include "hmx_internal.h"
+#include "hmx_dist_tile.h"
 
 namespace hmx {
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned long long u64;
 
 constexpr u64 KNN_EMPTY = ~0ull;      // above every key of a real distance (NaN included)
@@ -65,8 +64,8 @@ __global__ __launch_bounds__(256) void k_knn_ingest(const void* __restrict__ src
 // MG: PC groups of 16 the kernel is built for (P.NG <= MG of them are run); KP: list positions per query row (64 | 128, P.k <= KP)
 template <int MG, int KP>
 __global__ __launch_bounds__(256) void k_knn(KnnDev P) {
-  constexpr int S = 16 * MG + 4;                      // slab row stride in floats: S / 4 odd, so that the 16 rows of a b128 read spread over the banks
-  __shared__ __attribute__((aligned(16))) float slab[KNN_SLAB][S];
+  typedef DistTile<MG> Tile;                          // hmx_dist_tile.h: the A operand, the slab staging and the MFMA loop
+  __shared__ __attribute__((aligned(16))) float slab[KNN_SLAB][Tile::S];
   __shared__ float sxn[KNN_SLAB];
   __shared__ u64 lists[4][16][KP];
   const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, c = l & 15, g = l >> 4;
@@ -74,12 +73,8 @@ __global__ __launch_bounds__(256) void k_knn(KnnDev P) {
   const long long c0 = (long long)blockIdx.y * P.chunk, c1 = min(P.N, c0 + P.chunk);
   const int zs = P.zs, NG = P.NG, k = P.k;
 
-  f32x4 a[MG];                                        // A operand: query row q0 + c, PCs 16 t + 4 g + {0..3}
-#pragma unroll
-  for (int t = 0; t < MG; t++) {
-    a[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (t < NG && q0 + c < P.Nq && 16 * t + 4 * g < zs) a[t] = *(const f32x4*)(P.Q + (size_t)(q0 + c) * zs + 16 * t + 4 * g);
-  }
+  Tile DT;
+  DT.init(q0 + c < P.Nq ? P.Q + (size_t)(q0 + c) * zs : nullptr, zs, NG, slab);
   float qn[4], thr[4];                                // the lane's rows of the result tile: query rows q0 + 4 g + i
 #pragma unroll
   for (int i = 0; i < 4; i++) {
@@ -89,48 +84,16 @@ __global__ __launch_bounds__(256) void k_knn(KnnDev P) {
   }
   for (int q = 0; q < 16; q++)
     for (int p = l; p < KP; p += 64) lists[w][q][p] = KNN_EMPTY;
-  for (int i = tid; i < KNN_SLAB * S; i += 256) (&slab[0][0])[i] = 0.f;      // (the columns behind zs stay 0)
 
-  // staging: thread (row = tid >> 2, s = tid & 3) moves the float4 columns s, s + 4, ... of its slab row
-  const int srow = tid >> 2, nf4 = zs >> 2;
-  f32x4 pre[8];
-  float prexn = 0.f;
-  auto fetch = [&](long long base) {
-    const long long r = base + srow;
-#pragma unroll
-    for (int f = 0; f < 8; f++) {
-      const int col = (tid & 3) + 4 * f;
-      if (col < nf4) pre[f] = r < c1 ? *(const f32x4*)(P.X + (size_t)r * zs + 4 * col) : f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-    if (tid < KNN_SLAB) prexn = base + tid < c1 ? P.xn[base + tid] : 0.f;
-  };
-  fetch(c0);
+  DT.fetch(P.X, P.xn, c0, c1, zs);
   for (long long base = c0; base < c1; base += KNN_SLAB) {
     __syncthreads();                                  // the previous slab has been read by every wave
-#pragma unroll
-    for (int f = 0; f < 8; f++) {
-      const int col = (tid & 3) + 4 * f;
-      if (col < nf4) *(f32x4*)&slab[srow][4 * col] = pre[f];
-    }
-    if (tid < KNN_SLAB) sxn[tid] = prexn;
+    DT.stage(slab, sxn, zs);
     __syncthreads();
-    if (base + KNN_SLAB < c1) fetch(base + KNN_SLAB);
+    if (base + KNN_SLAB < c1) DT.fetch(P.X, P.xn, base + KNN_SLAB, c1, zs);
 
-    f32x4 acc[4];
-#pragma unroll
-    for (int tt = 0; tt < 4; tt++) acc[tt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int t = 0; t < MG; t++) {
-      if (t < NG) {
-#pragma unroll
-        for (int tt = 0; tt < 4; tt++) {
-          const f32x4 b = *(const f32x4*)&slab[16 * tt + c][16 * t + 4 * g];      // B operand: data row base + 16 tt + c, the same PCs
-#pragma unroll
-          for (int i = 0; i < 4; i++) acc[tt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[t][i], b[i], acc[tt], 0, 0, 0);
-        }
-      }
-    }
-    // acc[tt][i] = q . x of (query row q0 + 4 g + i, data row base + 16 tt + c)
+    f32x4 acc[4];                                     // acc[tt][i] = q . x of (query row q0 + 4 g + i, data row base + 16 tt + c)
+    DT.dots(slab, NG, acc);
     float d2[4][4];
     bool any = false;
 #pragma unroll
@@ -205,12 +168,6 @@ __global__ __launch_bounds__(256) void k_knn_merge(KnnDev P) {
   if (l + 64 < k) knn_store_result(P, qi, l + 64, e1);
 }
 
-__device__ __forceinline__ double lisi_wsum(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
-
 // LISI of cell (wave) over every label column.  Lane l holds neighbours l and l + 64 (m <= 128).  The weights P_j = exp(-D_j beta) / S are
 // found once per cell (binary search of beta for entropy ln(perplexity), as immunogenomics/LISI's compute_simpson_index does), then
 // every column's index is 1 / sum_j P_j (sum_j' P_j' [label_j' = label_j]) -- the sum over levels of the squared level masses, without a table of levels.
@@ -228,9 +185,9 @@ __global__ __launch_bounds__(256) void k_lisi(const int* __restrict__ idx, const
   auto hbeta = [&](double beta) {
     P0 = h0 ? exp(-D0 * beta) : 0.0;
     P1 = h1 ? exp(-D1 * beta) : 0.0;
-    const double S = lisi_wsum(P0 + P1);
+    const double S = wave_sum(P0 + P1);
     if (S == 0.0) { H = 0.0; P0 = P1 = 0.0; return; }
-    const double DP = lisi_wsum(D0 * P0 + D1 * P1);
+    const double DP = wave_sum(D0 * P0 + D1 * P1);
     H = log(S) + beta * DP / S;
     P0 /= S; P1 /= S;
   };
@@ -252,7 +209,7 @@ __global__ __launch_bounds__(256) void k_lisi(const int* __restrict__ idx, const
         s0 += a0 == aj ? pj : 0.0;
         s1 += a1 == aj ? pj : 0.0;
       }
-      r = 1.0 / lisi_wsum(P0 * s0 + P1 * s1);
+      r = 1.0 / wave_sum(P0 * s0 + P1 * s1);
     }
     if (l == 0) out[(size_t)cell * ncols + col] = r;
   }

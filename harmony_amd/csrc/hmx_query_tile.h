@@ -15,11 +15,6 @@ __device__ __forceinline__ float qwmax(float v) {
   for (int m = 32; m >= 1; m >>= 1) v = fmaxf(v, __shfl_xor(v, m, 64));
   return v;
 }
-__device__ __forceinline__ float qwsum(float v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
 
 // rows s .. s + cnt - 1 of Z into zt (pads and missing cells 0) and their inverse norms
 __device__ __forceinline__ void q_load_tile(const QueryDev& Q, const float* __restrict__ Z, int s, int cnt, float (*zt)[QZS], float* inv) {
@@ -33,7 +28,7 @@ __device__ __forceinline__ void q_load_tile(const QueryDev& Q, const float* __re
   for (int c = w; c < QT; c += blockDim.x >> 6) {
     float ss = 0.f;
     for (int j = l; j < zs; j += 64) ss += zt[c][j] * zt[c][j];
-    ss = qwsum(ss);
+    ss = wave_sum(ss);
     if (l == 0) inv[c] = ss > 0.f ? 1.0f / sqrtf(ss) : 0.f;
   }
   __syncthreads();
@@ -72,7 +67,7 @@ __device__ __forceinline__ void q_assign(const QueryDev& Q, int cnt, float (*zt)
     m = qwmax(m);
     float s = 0.f;
     for (int k = l; k < Q.K; k += 64) { const float e = expf(lg[c][k] - m); lg[c][k] = e; s += e; }
-    s = qwsum(s);
+    s = wave_sum(s);
     const float is = 1.0f / s;
     for (int k = l; k < Q.K; k += 64) lg[c][k] *= is;
   }

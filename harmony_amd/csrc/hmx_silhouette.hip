@@ -5,16 +5,16 @@
 //
 //   k_sil_gather      fp32 rows / squared norms in the given order (k_knn_ingest) -> the sorted, padded layout (pads 0);
 //   k_silhouette<MG>  workgroup = 64 query rows of the sorted order (16 per wave, A operand in registers); it streams the data rows of the
-//                     groups its rows belong to in 64-row slabs through LDS, as k_knn does: d2 = |q|^2 + |x|^2 - 2 q.x with the dot
-//                     product on v_mfma_f32_16x16x4_f32, dist = sqrt(max(d2, 0)), padding rows and self (by index) masked to 0.
+//                     groups its rows belong to in 64-row slabs through LDS, on the distance tile it shares with k_knn
+//                     (hmx_dist_tile.h): d2 = |q|^2 + |x|^2 - 2 q.x with the dot product on v_mfma_f32_16x16x4_f32,
+//                     dist = sqrt(max(d2, 0)), padding rows and self (by index) masked to 0.
 //                     A lane adds the distances of (its 4 query rows, its data column) in fp32 over at most SIL_FLUSH tiles; the 16
 //                     lanes that share a query row then reduce (4 more additions) into an fp64 segment sum.  At a segment's end the mean
 //                     is folded: a (own label, divisor count - 1) or a candidate of b = min (another label of the group).  O(1) state
 //                     per row, no atomics: the order of every addition is fixed by the layout -- bit-reproducible.
-#include "hmx_internal.h"
+#include "hmx_dist_tile.h"
 
 namespace hmx {
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));      // a SilTile in registers: x group, y label, z rows | last << 8, w count
 
 // v + the value of lane (lane ^ ...) / rotated within its row of 16 lanes: DPP, no LDS
@@ -46,8 +46,8 @@ __global__ __launch_bounds__(256) void k_sil_gather(const float* __restrict__ ro
 // MG: PC groups of 16 the kernel is built for (P.NG <= MG of them are run)
 template <int MG>
 __global__ __launch_bounds__(256) void k_silhouette(SilDev P) {
-  constexpr int S = 16 * MG + 4;                      // slab row stride in floats: S / 4 odd (k_knn)
-  __shared__ __attribute__((aligned(16))) float slab[KNN_SLAB][S];
+  typedef DistTile<MG> Tile;                          // hmx_dist_tile.h: the A operand, the slab staging and the MFMA loop
+  __shared__ __attribute__((aligned(16))) float slab[KNN_SLAB][Tile::S];
   __shared__ float sxn[KNN_SLAB];
   __shared__ i32x4 stile[KNN_SLAB / 16];
   const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, c = l & 15, g = l >> 4;
@@ -63,12 +63,8 @@ __global__ __launch_bounds__(256) void k_silhouette(SilDev P) {
   const long long c0 = 16ll * P.grange[2 * tiles[qt0].x], c1 = 16ll * P.grange[2 * tiles[min(qt0 + KNN_QROWS / 16, ntiles) - 1].x + 1];
   const int zs = P.zs, NG = P.NG;
 
-  f32x4 a[MG];                                        // A operand: query row q0 + c, PCs 16 t + 4 g + {0..3}
-#pragma unroll
-  for (int t = 0; t < MG; t++) {
-    a[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (t < NG && have && 16 * t + 4 * g < zs) a[t] = *(const f32x4*)(P.X + (size_t)(q0 + c) * zs + 16 * t + 4 * g);
-  }
+  Tile DT;
+  DT.init(have ? P.X + (size_t)(q0 + c) * zs : nullptr, zs, NG, slab);
   float qn[4], part[4];                               // the lane's rows of the result tile: query rows q0 + 4 g + i
   double seg[4], av[4], bv[4];
 #pragma unroll
@@ -79,51 +75,22 @@ __global__ __launch_bounds__(256) void k_silhouette(SilDev P) {
     bv[i] = INFINITY;
   }
   int nacc = 0;                                       // tiles added into part[] since the last reduction (wave-uniform)
-  for (int i = tid; i < KNN_SLAB * S; i += 256) (&slab[0][0])[i] = 0.f;      // (the columns behind zs stay 0)
 
-  // staging: thread (row = tid >> 2, s = tid & 3) moves the float4 columns s, s + 4, ... of its slab row
-  const int srow = tid >> 2, nf4 = zs >> 2;
-  f32x4 pre[8];
-  float prexn = 0.f;
-  i32x4 pretile = none;
+  i32x4 pretile = none;                               // the slab's four SilTiles travel with it: fetched and staged next to the rows
   auto fetch = [&](long long base) {
-    const long long r = base + srow;
-#pragma unroll
-    for (int f = 0; f < 8; f++) {
-      const int col = (tid & 3) + 4 * f;
-      if (col < nf4) pre[f] = r < c1 ? *(const f32x4*)(P.X + (size_t)r * zs + 4 * col) : f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-    if (tid < KNN_SLAB) prexn = base + tid < c1 ? P.xn[base + tid] : 0.f;
+    DT.fetch(P.X, P.xn, base, c1, zs);
     if (tid < KNN_SLAB / 16) pretile = base + 16 * tid < c1 ? tiles[(base >> 4) + tid] : none;
   };
   fetch(c0);
   for (long long base = c0; base < c1; base += KNN_SLAB) {
     __syncthreads();                                  // the previous slab has been read by every wave
-#pragma unroll
-    for (int f = 0; f < 8; f++) {
-      const int col = (tid & 3) + 4 * f;
-      if (col < nf4) *(f32x4*)&slab[srow][4 * col] = pre[f];
-    }
-    if (tid < KNN_SLAB) sxn[tid] = prexn;
+    DT.stage(slab, sxn, zs);
     if (tid < KNN_SLAB / 16) stile[tid] = pretile;
     __syncthreads();
     if (base + KNN_SLAB < c1) fetch(base + KNN_SLAB);
 
-    f32x4 acc[4];
-#pragma unroll
-    for (int tt = 0; tt < 4; tt++) acc[tt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int t = 0; t < MG; t++) {
-      if (t < NG) {
-#pragma unroll
-        for (int tt = 0; tt < 4; tt++) {
-          const f32x4 b = *(const f32x4*)&slab[16 * tt + c][16 * t + 4 * g];      // B operand: data row base + 16 tt + c, the same PCs
-#pragma unroll
-          for (int i = 0; i < 4; i++) acc[tt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[t][i], b[i], acc[tt], 0, 0, 0);
-        }
-      }
-    }
-    // acc[tt][i] = q . x of (query row q0 + 4 g + i, data row base + 16 tt + c)
+    f32x4 acc[4];                                     // acc[tt][i] = q . x of (query row q0 + 4 g + i, data row base + 16 tt + c)
+    DT.dots(slab, NG, acc);
 #pragma unroll
     for (int tt = 0; tt < 4; tt++) {
       const i32x4 T = stile[tt];

@@ -10,46 +10,9 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib
-from .harmony_obj import HarmonyError
-from .ui import _columns, as_factor
+from ._call import MAX_D, _column, _factor, _Handle, _rows
 
 MAX_K = 128
-MAX_D = 128
-
-
-class _Handle(object):
-    """a handle that lives for one call: it carries the device, the stream and the error text"""
-
-    def __init__(self, device=None):
-        self.lib = _lib.load()
-        self.h = C.c_void_p(self.lib.hmx_create())
-        if not self.h:
-            raise HarmonyError("hmx_create failed")
-        if device is not None and self.lib.hmx_set_int(self.h, b"device", int(device)) != 0:
-            raise HarmonyError("set device: " + self.lib.hmx_last_error(self.h).decode())
-
-    def check(self, status, what):
-        if status != 0:
-            raise HarmonyError("%s failed (status %d): %s" % (what, status, self.lib.hmx_last_error(self.h).decode()))
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.lib.hmx_destroy(self.h)
-        self.h = None
-
-
-def _rows(X, what):
-    """cells x PCs -> (C-contiguous float64 / float32 array, dtype code)"""
-    X = np.asarray(X)
-    if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] < 1:
-        raise ValueError("%s must be a cells x PCs matrix" % what)
-    if X.shape[1] > MAX_D:
-        raise ValueError("%s has %d PCs: at most %d are supported" % (what, X.shape[1], MAX_D))
-    f32 = X.dtype == np.float32
-    return np.ascontiguousarray(X, dtype=np.float32 if f32 else np.float64), (1 if f32 else 0)
 
 
 def _label_codes(label_codes, n_levels, N):
@@ -71,22 +34,13 @@ def _label_codes(label_codes, n_levels, N):
 
 def _factor_columns(meta_data, label_colnames, N):
     """the label columns of meta_data through ui.as_factor: (codes n_cols x N, n_levels, [levels])"""
-    cols = _columns(meta_data)
-    if cols is None:
-        raise ValueError("meta_data must be a data.frame-like object or a mapping of columns")
     if isinstance(label_colnames, str):
         label_colnames = [label_colnames]
-    label_colnames = list(label_colnames)
-    if not label_colnames or any(c not in cols for c in label_colnames):
-        raise ValueError("label_colnames must name columns of meta_data")
+    names = list(label_colnames) or [None]              # (no name at all: refused as a name that is no column)
+    values = [_column(meta_data, c, missing="label_colnames must name columns of meta_data") for c in names]
     codes, n_levels, levels = [], [], []
-    for c in label_colnames:
-        v = np.asarray(cols[c])
-        if v.ndim != 1 or v.shape[0] != N:
-            raise ValueError("column %r has %s labels for %d cells" % (c, v.shape, N))
-        if v.dtype.kind == "f" and np.any(np.isnan(v)) or v.dtype.kind == "O" and any(x is None or x != x for x in v):
-            raise ValueError("column %r holds NaN / missing labels" % c)
-        cd, lv = as_factor(v)
+    for c, v in zip(names, values):
+        cd, lv = _factor(v, N, "column %r" % c, wrong_shape="%(what)s has %(shape)s labels for %(N)d cells")
         codes.append(cd)
         n_levels.append(len(lv))
         levels.append(lv)
@@ -190,18 +144,13 @@ def harmony_lisi(obj, meta_data, label_colnames, perplexity=30):
     return _compute_lisi(obj._lib, obj._h, obj._check, None, 0, N, 0, codes, n_levels, perplexity)
 
 
-
 def knn_predict(query, reference, reference_labels, k=5, device=None):
     """Symphony's knnPredict: the label of every query cell by majority vote over its k nearest reference cells (both cells x PCs, in the
     reference's corrected space: Z_corr of the fit and of map_query).  Ties go to the smallest level in sorted order.  Returns (labels,
     share): the winning label and the fraction of the k votes it got."""
-    ref_labels = np.asarray(reference_labels)
     R = np.asarray(reference)
-    if ref_labels.ndim != 1 or R.ndim != 2 or ref_labels.shape[0] != R.shape[0]:
-        raise ValueError("reference_labels must hold one label per reference cell")
-    if ref_labels.dtype.kind == "f" and np.any(np.isnan(ref_labels)) or ref_labels.dtype.kind == "O" and any(x is None or x != x for x in ref_labels):
-        raise ValueError("reference_labels holds NaN / missing labels")
-    codes, levels = as_factor(ref_labels)
+    codes, levels = _factor(reference_labels, R.shape[0] if R.ndim == 2 else -1, "reference_labels",
+                            wrong_shape="reference_labels must hold one label per reference cell")
     idx, _ = knn(reference, k, query=query, device=device)
     votes = np.zeros((idx.shape[0], len(levels)), dtype=np.int64)
     np.add.at(votes, (np.arange(idx.shape[0])[:, None], codes[idx]), 1)

@@ -12,6 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._call import _Handle
 from .harmony_obj import HarmonyError
 from .utils import _message
 
@@ -249,7 +250,6 @@ def project_query(counts, genes, loadings, totals=None, out="host", device=None,
     if _handle is not None:
         run(_handle)
     else:
-        from .metrics import _Handle
         with _Handle(device) as h:
             run(h)
     if out == "device":

@@ -10,28 +10,7 @@ import ctypes as C
 
 import numpy as np
 
-from .metrics import _Handle, _rows
-from .ui import _columns, as_factor
-
-
-def _factor(values, N, what):
-    """one label per cell through ui.as_factor: (int32 codes, levels); NaN / missing labels are refused"""
-    v = np.asarray(values)
-    if v.ndim != 1 or v.shape[0] != N:
-        raise ValueError("%s must hold one label per cell (%d), got shape %s" % (what, N, v.shape))
-    if v.dtype.kind == "f" and np.any(np.isnan(v)) or v.dtype.kind == "O" and any(x is None or x != x for x in v):
-        raise ValueError("%s holds NaN / missing labels" % what)
-    codes, levels = as_factor(v)
-    return np.ascontiguousarray(codes, dtype=np.int32), levels
-
-
-def _column(meta_data, name, N):
-    cols = _columns(meta_data)
-    if cols is None:
-        raise ValueError("meta_data must be a data.frame-like object or a mapping of columns")
-    if not isinstance(name, str) or name not in cols:
-        raise ValueError("%r does not name a column of meta_data" % (name,))
-    return _factor(cols[name], N, "column %r" % name)
+from ._call import _factor, _factor_column, _Handle, _rows
 
 
 def _call(lib, handle, check, X, xdt, N, d, codes, n_levels, gcodes, n_groups, return_ab):
@@ -72,7 +51,7 @@ def silhouette_label(X, meta_data, label_col, rescale=True, device=None):
     (1: the labels are apart)."""
     X, xdt = _rows(X, "X")
     N, d = X.shape
-    codes, levels = _column(meta_data, label_col, N)
+    codes, levels = _factor_column(meta_data, label_col, N)
     if len(levels) < 2:
         raise ValueError("silhouette widths need at least two labels, got %d" % len(levels))
     with _Handle(device) as h:
@@ -102,8 +81,8 @@ def silhouette_batch(X, meta_data, batch_col, label_col, rescale=True, device=No
     batch_asw: (score, {level of label_col: mean}); with rescale=True, 1 means the batches are mixed within every label."""
     X, xdt = _rows(X, "X")
     N, d = X.shape
-    bcodes, blevels = _column(meta_data, batch_col, N)
-    gcodes, glevels = _column(meta_data, label_col, N)
+    bcodes, blevels = _factor_column(meta_data, batch_col, N)
+    gcodes, glevels = _factor_column(meta_data, label_col, N)
     with _Handle(device) as h:
         s = _call(h.lib, h.h, h.check, X, xdt, N, d, bcodes, len(blevels), gcodes, len(glevels), False)
     return batch_asw(s, bcodes, gcodes, glevels, rescale)
@@ -112,12 +91,12 @@ def silhouette_batch(X, meta_data, batch_col, label_col, rescale=True, device=No
 def harmony_silhouette(obj, meta_data, label_col, group_col=None, return_ab=False):
     """Harmony.silhouette: silhouette widths of the handle's current Z_corr (a fitted handle or a mapped query), read where it lives in HBM"""
     N = int(obj._scalar("N_local"))
-    codes, levels = _column(meta_data, label_col, N)
+    codes, levels = _factor_column(meta_data, label_col, N)
     gcodes, n_groups = None, 1
     if group_col is None:
         if len(levels) < 2:
             raise ValueError("silhouette widths need at least two labels, got %d" % len(levels))
     else:
-        gcodes, glevels = _column(meta_data, group_col, N)
+        gcodes, glevels = _factor_column(meta_data, group_col, N)
         n_groups = len(glevels)
     return _call(obj._lib, obj._h, obj._check, None, 0, N, 0, codes, len(levels), gcodes, n_groups, return_ab)

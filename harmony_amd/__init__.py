@@ -8,6 +8,7 @@ from .harmony_obj import Harmony, HarmonyError
 from .mapping import HarmonyReference, map_query, mapping_confidence
 from .metrics import compute_lisi, knn, knn_predict, lisi_from_knn
 from .options import harmony_options
+from .pca import fit_loadings, gene_stats
 from .project import HarmonyLoadings, map_query_counts, project_query
 from .silhouette import silhouette_batch, silhouette_label, silhouette_samples
 from .ui import RunHarmony, prepare_setup_args
@@ -15,4 +16,4 @@ from .utils import harmonize
 
 __all__ = ["RunHarmony", "harmony_options", "Harmony", "HarmonyError", "harmonize", "prepare_setup_args", "map_query",
            "HarmonyReference", "mapping_confidence", "knn", "compute_lisi", "lisi_from_knn", "knn_predict",
-           "silhouette_samples", "silhouette_label", "silhouette_batch", "HarmonyLoadings", "project_query", "map_query_counts"]
+           "silhouette_samples", "silhouette_label", "silhouette_batch", "HarmonyLoadings", "project_query", "map_query_counts", "gene_stats", "fit_loadings"]

@@ -90,6 +90,16 @@ PROJECT_SIGNATURES = {
                                      _dp, _dp, _dp, C.c_int32, C.c_int32, C.c_double, C.c_double, _dp, C.c_void_p, C.c_int32]),
 }
 
+# the symbols include/harmony_mi355x_pca.h declares (gene statistics; the standardised matrix as an operator)
+PCA_SIGNATURES = {
+    "hmx_gene_stats": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, _dp,
+                                 _lp, _dp, _dp, _dp]),
+    "hmx_pca_prepare": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, _ip, _dp, _dp,
+                                  C.c_int32, C.c_double, C.c_double, _dp]),
+    "hmx_pca_apply": (C.c_int, [C.c_void_p, _dp, C.c_int32, _dp, C.c_void_p, C.c_int32]),
+    "hmx_pca_release": (C.c_int, [C.c_void_p]),
+}
+
 _lib = None
 
 
@@ -108,7 +118,7 @@ def load():
             "harmony_amd has no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in (list(SIGNATURES.items()) + list(METRICS_SIGNATURES.items()) + list(SILHOUETTE_SIGNATURES.items())
-                              + list(CONFIDENCE_SIGNATURES.items()) + list(PROJECT_SIGNATURES.items())):
+                              + list(CONFIDENCE_SIGNATURES.items()) + list(PROJECT_SIGNATURES.items()) + list(PCA_SIGNATURES.items())):
         fn = getattr(lib, name)  # AttributeError if the ABI and the header drift apart
         fn.restype = res
         fn.argtypes = args

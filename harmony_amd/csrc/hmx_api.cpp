@@ -7,6 +7,7 @@
 #include "../../include/harmony_mi355x_silhouette.h"  // (silhouette widths: hmx_api_silhouette.inc)
 #include "../../include/harmony_mi355x_confidence.h"  // (reference moments, mapping confidence: hmx_api_confidence.inc)
 #include "../../include/harmony_mi355x_project.h"  // (count projection: hmx_api_project.inc)
+#include "../../include/harmony_mi355x_pca.h"  // (gene statistics, the standardised matrix as an operator: hmx_api_pca.inc)
 #include "hmx_internal.h"
 #include "hmx_rrng.h"
 #include "hmx_plan.h"
@@ -24,6 +25,7 @@
 #include <cstring>
 #include <deque>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <numeric>
 #include <set>
@@ -358,3 +360,4 @@ int hmx_moe_correct_ridge(hmx_ctx* ctx) {  // src/harmony.cpp:345-638
 #include "hmx_api_silhouette.inc"
 #include "hmx_api_confidence.inc"
 #include "hmx_api_project.inc"
+#include "hmx_api_pca.inc"

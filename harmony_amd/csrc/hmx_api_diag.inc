@@ -171,6 +171,7 @@ int64_t hmx_get(hmx_ctx* ctx, const char* field, double* out, int64_t cap) {
   if (f == "dot_bf") return scalar(ctx->D.dot_bf ? 1.0 : 0.0);     // split-bf16 tile kernels offered (each launch still checks its LDS budget)
   if (f == "sold_carry") return scalar(ctx->carry_ok ? 1.0 : 0.0);
   if (f == "project_slabs") return scalar((double)ctx->project_slabs);
+  if (f == "pca_entries") return scalar((double)ctx->pca_entries);
   if (f == "carried_rounds") return scalar((double)ctx->carried_rounds);
   if (f == "rounds_without_R") return scalar((double)ctx->rounds_without_R);
   if (f == "chain_rounds") return scalar((double)ctx->chain_rounds);

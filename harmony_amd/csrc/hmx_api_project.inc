@@ -49,6 +49,89 @@ const char* proj_violation(unsigned flag) {
   return "a stored value is not finite";
 }
 
+// One pass over a CSR matrix of `N` rows: launch(indptr, base, nnz, indices, data, nrows, row0) once for a device-resident matrix, once per slab
+// of whole cells for a host-resident one -- two sets of staging buffers (owned by `B`), the copy of slab t + 1 (upload stream) beside the kernel
+// of slab t.  Returns with both streams drained.  (hmx_project_counts; hmx_gene_stats and hmx_pca_prepare in hmx_api_pca.inc)
+template <class F>
+int csr_sweep(hmx_ctx* ctx, CallBufs& B, int64_t N, const int64_t* indptr, const int32_t* indices, const void* data, int esz, int32_t csr_location,
+              const char* what, F launch) {
+  hipStream_t st = ctx->L.stream;
+  if (csr_location == HMX_DEVICE) {
+    long long nnz = 0;
+    HIPCHK(hipMemcpyAsync(&nnz, indptr + N, sizeof(nnz), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (nnz < 0) return fail(ctx, HMX_ERR_ARG, "indptr[Nq] is negative");
+    launch((const long long*)indptr, (long long)0, nnz, indices, data, (long long)N, (long long)0); KCHK();
+    return 0;
+  }
+  // ---- slabs of whole cells through two sets of staging buffers
+  const int64_t cap_bytes = ctx->project_slab_bytes > 0 ? ctx->project_slab_bytes : PROJ_SLAB_BYTES;
+  const std::vector<ProjSlab> S = proj_slabs(indptr, N, std::max<int64_t>(1, cap_bytes / (4 + esz)));
+  int64_t max_nnz = 1, max_rows = 1;
+  for (const ProjSlab& s : S) { max_nnz = std::max(max_nnz, indptr[s.row1] - indptr[s.row0]); max_rows = std::max(max_rows, s.row1 - s.row0); }
+  ctx->project_slabs = (int64_t)S.size();
+  const int nset = S.size() > 1 ? 2 : 1;
+  long long* sptr[2]; int* sidx[2]; char* sval[2];
+  for (int s = 0; s < nset; s++) {
+    HIPCHK(B.get(&sptr[s], (size_t)max_rows + 1)); HIPCHK(B.get(&sidx[s], (size_t)max_nnz)); HIPCHK(B.get(&sval[s], (size_t)max_nnz * esz));
+  }
+  struct Side {      // the upload stream and the events of one pass
+    hipStream_t up = nullptr; hipEvent_t uploaded[2] = {nullptr, nullptr}, consumed[2] = {nullptr, nullptr};
+    ~Side() {
+      for (int s = 0; s < 2; s++) { if (uploaded[s]) (void)hipEventDestroy(uploaded[s]); if (consumed[s]) (void)hipEventDestroy(consumed[s]); }
+      if (up) (void)hipStreamDestroy(up);
+    }
+  } Y;
+  HIPCHK(hipStreamCreateWithFlags(&Y.up, hipStreamNonBlocking));
+  for (int s = 0; s < nset; s++) {
+    HIPCHK(hipEventCreateWithFlags(&Y.uploaded[s], hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&Y.consumed[s], hipEventDisableTiming));
+  }
+  HIPCHK(hipEventRecord(Y.uploaded[0], st));      // the tables are in place before the first kernel: same stream; and the upload stream
+  HIPCHK(hipStreamWaitEvent(Y.up, Y.uploaded[0], 0));      // starts behind them only to keep the order of the copies simple
+  hipError_t e = hipSuccess;
+  for (size_t t = 0; t < S.size() && e == hipSuccess; t++) {
+    const int s = (int)(t & 1);
+    const int64_t r0 = S[t].row0, nr = S[t].row1 - r0, base = indptr[r0], cnt = indptr[S[t].row1] - base;
+    if (t >= 2) e = hipStreamWaitEvent(Y.up, Y.consumed[s], 0);      // the kernel of slab t - 2 has read this set
+    if (e == hipSuccess) e = hipMemcpyAsync(sptr[s], indptr + r0, (size_t)(nr + 1) * sizeof(int64_t), hipMemcpyHostToDevice, Y.up);
+    if (e == hipSuccess && cnt) e = hipMemcpyAsync(sidx[s], indices + base, (size_t)cnt * sizeof(int32_t), hipMemcpyHostToDevice, Y.up);
+    if (e == hipSuccess && cnt) e = hipMemcpyAsync(sval[s], (const char*)data + (size_t)base * esz, (size_t)cnt * esz, hipMemcpyHostToDevice, Y.up);
+    if (e == hipSuccess) e = hipEventRecord(Y.uploaded[s], Y.up);
+    if (e == hipSuccess) e = hipStreamWaitEvent(st, Y.uploaded[s], 0);
+    if (e != hipSuccess) break;
+    launch((const long long*)sptr[s], (long long)base, (long long)cnt, (const int*)sidx[s], (const void*)sval[s], (long long)nr, (long long)r0);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipEventRecord(Y.consumed[s], st);
+  }
+  const hipError_t e1 = hipStreamSynchronize(Y.up), e2 = hipStreamSynchronize(st);      // (the buffers are released by the caller: nothing may still use them)
+  if (e != hipSuccess || e1 != hipSuccess || e2 != hipSuccess)
+    return fail(ctx, HMX_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e != hipSuccess ? e : e1 != hipSuccess ? e1 : e2));
+  return 0;
+}
+
+// the checks of a count matrix's description that need no device, and the host's pass over a host-resident matrix
+int csr_args(hmx_ctx* ctx, int64_t N, int32_t G_all, const int64_t* indptr, const int32_t* indices, const void* data, int32_t data_dtype,
+             int32_t csr_location, double scale, const double* totals) {
+  if (!indptr || !indices || !data) return fail(ctx, HMX_ERR_ARG, "null argument");
+  if (N <= 0 || G_all <= 0) return fail(ctx, HMX_ERR_ARG, "non-positive dimension");
+  if (data_dtype != HMX_F32 && data_dtype != HMX_F64) return fail(ctx, HMX_ERR_ARG, "data_dtype must be HMX_F32 or HMX_F64");
+  if (csr_location != HMX_HOST && csr_location != HMX_DEVICE) return fail(ctx, HMX_ERR_ARG, "a location must be HMX_HOST or HMX_DEVICE");
+  if (G_all > (1 << 24)) return fail(ctx, HMX_ERR_LIMIT, "supported envelope: G, G_all <= 2^24");
+  if (N > 2000000000ll) return fail(ctx, HMX_ERR_LIMIT, "at most 2e9 cells");
+  if (!(scale > 0) || !std::isfinite(scale)) return fail(ctx, HMX_ERR_ARG, "scale must be positive and finite");
+  if (totals)
+    for (int64_t i = 0; i < N; i++)
+      if (!(totals[i] >= 0) || !std::isfinite(totals[i])) return fail(ctx, HMX_ERR_ARG, "totals must be non-negative and finite (cell " + std::to_string(i) + ")");
+  return 0;
+}
+int csr_host_pass(hmx_ctx* ctx, int64_t N, int32_t G_all, const int64_t* indptr, const int32_t* indices) {
+  int64_t where = 0;
+  const int v = proj_validate(indptr, indices, N, G_all, &where);
+  if (v == 1) return fail(ctx, HMX_ERR_ARG, "indptr is not monotone from 0 (row " + std::to_string(where) + ")");
+  if (v == 2) return fail(ctx, HMX_ERR_ARG, "a column index is outside [0, G_all) (entry " + std::to_string(where) + ")");
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -127,58 +210,11 @@ int hmx_project_counts(hmx_ctx* ctx, int64_t Nq, int32_t G_all, const int64_t* i
   P.f64 = data_dtype == HMX_F64; P.slot = dslot; P.U = dU; P.inv_sd = dinv; P.cap = dcap; P.b = db; P.totals = dtot; P.scale = scale;
   P.G_all = G_all; P.G = G; P.d = d; P.out = dout; P.flag = dflag;
 
-  if (csr_location == HMX_DEVICE) {
-    long long nnz = 0;
-    HIPCHK(hipMemcpyAsync(&nnz, indptr + Nq, sizeof(nnz), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (nnz < 0) return fail(ctx, HMX_ERR_ARG, "indptr[Nq] is negative");
-    P.indptr = (const long long*)indptr; P.base = 0; P.nnz = nnz; P.indices = indices; P.data = data; P.nrows = Nq; P.row0 = 0;
-    l_project(ctx->L, P, st); KCHK();
-  } else {
-    // ---- slabs of whole cells through two sets of staging buffers: the copy of slab t + 1 (upload stream) runs beside the kernel of slab t
-    const int64_t cap_bytes = ctx->project_slab_bytes > 0 ? ctx->project_slab_bytes : PROJ_SLAB_BYTES;
-    const std::vector<ProjSlab> S = proj_slabs(indptr, Nq, std::max<int64_t>(1, cap_bytes / (4 + esz)));
-    int64_t max_nnz = 1, max_rows = 1;
-    for (const ProjSlab& s : S) { max_nnz = std::max(max_nnz, indptr[s.row1] - indptr[s.row0]); max_rows = std::max(max_rows, s.row1 - s.row0); }
-    ctx->project_slabs = (int64_t)S.size();
-    const int nset = S.size() > 1 ? 2 : 1;
-    long long* sptr[2]; int* sidx[2]; char* sval[2];
-    for (int s = 0; s < nset; s++) {
-      HIPCHK(B.get(&sptr[s], (size_t)max_rows + 1)); HIPCHK(B.get(&sidx[s], (size_t)max_nnz)); HIPCHK(B.get(&sval[s], (size_t)max_nnz * esz));
-    }
-    struct Side {      // the upload stream and the events of one call
-      hipStream_t up = nullptr; hipEvent_t uploaded[2] = {nullptr, nullptr}, consumed[2] = {nullptr, nullptr};
-      ~Side() {
-        for (int s = 0; s < 2; s++) { if (uploaded[s]) (void)hipEventDestroy(uploaded[s]); if (consumed[s]) (void)hipEventDestroy(consumed[s]); }
-        if (up) (void)hipStreamDestroy(up);
-      }
-    } Y;
-    HIPCHK(hipStreamCreateWithFlags(&Y.up, hipStreamNonBlocking));
-    for (int s = 0; s < nset; s++) {
-      HIPCHK(hipEventCreateWithFlags(&Y.uploaded[s], hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&Y.consumed[s], hipEventDisableTiming));
-    }
-    HIPCHK(hipEventRecord(Y.uploaded[0], st));      // the tables are in place before the first kernel: same stream; and the upload stream
-    HIPCHK(hipStreamWaitEvent(Y.up, Y.uploaded[0], 0));      // starts behind them only to keep the order of the copies simple
-    hipError_t e = hipSuccess;
-    for (size_t t = 0; t < S.size() && e == hipSuccess; t++) {
-      const int s = (int)(t & 1);
-      const int64_t r0 = S[t].row0, nr = S[t].row1 - r0, base = indptr[r0], cnt = indptr[S[t].row1] - base;
-      if (t >= 2) e = hipStreamWaitEvent(Y.up, Y.consumed[s], 0);      // the kernel of slab t - 2 has read this set
-      if (e == hipSuccess) e = hipMemcpyAsync(sptr[s], indptr + r0, (size_t)(nr + 1) * sizeof(int64_t), hipMemcpyHostToDevice, Y.up);
-      if (e == hipSuccess && cnt) e = hipMemcpyAsync(sidx[s], indices + base, (size_t)cnt * sizeof(int32_t), hipMemcpyHostToDevice, Y.up);
-      if (e == hipSuccess && cnt) e = hipMemcpyAsync(sval[s], (const char*)data + (size_t)base * esz, (size_t)cnt * esz, hipMemcpyHostToDevice, Y.up);
-      if (e == hipSuccess) e = hipEventRecord(Y.uploaded[s], Y.up);
-      if (e == hipSuccess) e = hipStreamWaitEvent(st, Y.uploaded[s], 0);
-      if (e != hipSuccess) break;
-      P.indptr = sptr[s]; P.base = base; P.nnz = cnt; P.indices = sidx[s]; P.data = sval[s]; P.nrows = nr; P.row0 = r0;
-      l_project(ctx->L, P, st);
-      e = hipGetLastError();
-      if (e == hipSuccess) e = hipEventRecord(Y.consumed[s], st);
-    }
-    const hipError_t e1 = hipStreamSynchronize(Y.up), e2 = hipStreamSynchronize(st);      // (the buffers are released below: nothing may still use them)
-    if (e != hipSuccess || e1 != hipSuccess || e2 != hipSuccess)
-      return fail(ctx, HMX_ERR_DEVICE, std::string("project: ") + hipGetErrorString(e != hipSuccess ? e : e1 != hipSuccess ? e1 : e2));
-  }
+  CHK(csr_sweep(ctx, B, Nq, indptr, indices, data, esz, csr_location, "project",
+                [&](const long long* ptr, long long base, long long nnz, const int* idx, const void* val, long long nrows, long long row0) {
+                  P.indptr = ptr; P.base = base; P.nnz = nnz; P.indices = idx; P.data = val; P.nrows = nrows; P.row0 = row0;
+                  l_project(ctx->L, P, st);
+                }));
   unsigned flag = 0;
   HIPCHK(hipMemcpyAsync(&flag, dflag, sizeof(flag), hipMemcpyDeviceToHost, st));
   if (out_location == HMX_HOST) HIPCHK(hipMemcpyAsync(out, dout, (size_t)Nq * d * sizeof(float), hipMemcpyDeviceToHost, st));

@@ -378,6 +378,45 @@ struct ProjDev {
 };
 void l_project(const Launch& L, const ProjDev& P, hipStream_t stream);
 
+// ---- the reference's PCA from raw counts (hmx_pca.hip): gene statistics, the compact lists, P = S V and W = S^T P ---------------------------
+constexpr int PCA_STAT_GENES = 7680;       // genes whose three integer tables a workgroup of the statistics keeps in LDS (20 bytes each: 150 KB)
+constexpr int PCA_TILE = 256;              // cells per tile of the transposition: fixed, so the gene-major order does not depend on a grid
+constexpr int PCA_RUN = 256;               // entries of a gene's list added in fp32 before the sums go to fp64
+constexpr int PCA_CHUNK = 8192;            // entries of one gene's list a wave sums: a multiple of PCA_RUN
+constexpr int PCA_COLSUM_ROWS = 1024;      // rows of P one thread adds per column before the ranges are added
+struct PcaStatDev {
+  ProjDev C;                               // the rows of this launch (slot, U, inv_sd, cap, b, out unused)
+  float ymax; double q1, q2;               // y is clamped to ymax; y q1 and y^2 q2 (powers of two) are rounded to integers
+  unsigned long long* s1; unsigned long long* s2; unsigned long long* n;      // [G_all]
+};
+void l_gene_stats(const PcaStatDev& S, hipStream_t stream);
+struct PcaCompactDev {
+  ProjDev C;                               // the rows of this launch (U, b, out unused)
+  long long* cnt;                          // [N] count pass: contributing entries of every cell
+  const long long* cptr; long long entries;      // [N + 1] fill pass: where a cell's entries go, and their total
+  int* cj; float* cw;                      // [entries]
+};
+void l_pca_compact(const PcaCompactDev& S, bool fill, hipStream_t stream);
+struct PcaListDev {
+  const long long* cptr; const int* cj; const float* cw; long long N; int G;      // the cell-major list
+  long long ntiles; int* hist;             // [ntiles][G] entries of gene g in tile t, then (k_pca_scan) in the tiles before t
+  long long* glen;                         // [G] entries of a gene
+  const long long* gptr; int* tcell; float* tw;      // [G + 1] segments of the gene-major list, [entries] cell and weight
+};
+void l_pca_transpose_count(const PcaListDev& T, hipStream_t stream);
+void l_pca_transpose_place(const PcaListDev& T, hipStream_t stream);
+struct PcaChunk { int gene; int len; long long start; };      // entries [start, start + len) of the gene-major list, all of one gene
+struct PcaApplyDev {
+  const long long* cptr; const int* cj; const float* cw; long long N; int G, k, zs;      // zs = 64 ceil(k / 64)
+  const float* V; const double* b;         // [G][zs] fp32 (pads 0), [k]
+  float* Ppad; float* out;                 // [N][zs] P (pads 0); [N][k] the caller's copy or nullptr
+  long long nranges; double* colpart; double* colsum;      // [nranges][zs], [zs]
+  const int* tcell; const float* tw; const PcaChunk* chunk; long long nchunks; const int* cstart;      // cstart [G + 1]: the chunks of a gene
+  double* part;                            // [nchunks][zs]
+  const double* ratio; double* W;          // [G] mean / sd (0: no gene maps to the column), [G][k]
+};
+void l_pca_apply(const PcaApplyDev& A, hipStream_t stream);
+
 // the sum over the 64 lanes of a wave, in every one of them (xor butterfly: the same order of additions in every lane)
 template <class T>
 __device__ __forceinline__ T wave_sum(T v) {

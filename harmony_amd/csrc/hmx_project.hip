@@ -13,36 +13,9 @@
 //                       on results, two calls are bit-identical.
 //   Out-of-contract input never leaves the arrays: an indptr pair outside 0 <= lo <= hi <= nnz empties the row, a column outside [0, G_all) or a
 //   negative / non-finite value makes the entry non-contributing, and the kind of violation is or-ed into one flag word the host reads back.
-#include "hmx_internal.h"
+#include "hmx_proj_row.h"      // (proj_wave_sync, proj_row_total, proj_rate, proj_weight, proj_drain: shared with hmx_pca.hip)
 
 namespace hmx {
-
-__device__ __forceinline__ void proj_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// n <= 64 queued entries, lane l holding entry l (w = 0, j = 0 behind n), eight at a time in queue order
-template <int NC>
-__device__ __forceinline__ void proj_drain(const float* __restrict__ U, int zs, int lane, int jj, float ww, int n, float (&acc)[NC]) {
-  for (int g = 0; g < n; g += 8) {
-    int j[8]; float w[8], u[8][NC];
-#pragma unroll
-    for (int k = 0; k < 8; k++) {
-      j[k] = __builtin_amdgcn_readlane(jj, g + k);
-      w[k] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ww), g + k));
-    }
-#pragma unroll
-    for (int k = 0; k < 8; k++) {
-#pragma unroll
-      for (int c = 0; c < NC; c++) u[k][c] = U[(size_t)j[k] * zs + lane + 64 * c];
-    }
-#pragma unroll
-    for (int k = 0; k < 8; k++) {
-#pragma unroll
-      for (int c = 0; c < NC; c++) acc[c] = fmaf(w[k], u[k][c], acc[c]);
-    }
-  }
-}
 
 template <int NC, bool F64>
 __global__ __launch_bounds__(256) void k_project(ProjDev P) {
@@ -56,20 +29,8 @@ __global__ __launch_bounds__(256) void k_project(ProjDev P) {
     long long lo = P.indptr[i] - P.base, hi = P.indptr[i + 1] - P.base;
     if (lo < 0 || hi < lo || hi > P.nnz) { bad |= PROJ_BAD_INDPTR; lo = hi = 0; }
     // ---- phase 1: the library size
-    double T;
-    if (P.totals) T = P.totals[P.row0 + i];
-    else {
-      double t = 0.0;
-#pragma unroll 4
-      for (long long e = lo + lane; e < hi; e += 64) {
-        const double x = F64 ? ((const double*)P.data)[e] : (double)((const float*)P.data)[e];
-        if (x >= 0 && x <= 3.0e38) t += x;      // (anything else is reported by phase 2)
-      }
-#pragma unroll
-      for (int m = 32; m >= 1; m >>= 1) t += __shfl_xor(t, m, 64);
-      T = t;
-    }
-    const float r = T > 0 ? fminf((float)(P.scale / T), 3.0e38f) : 0.f;      // (T = 0: an empty row or stored zeros, y = 0 and P = b)
+    const double T = P.totals ? P.totals[P.row0 + i] : proj_row_total<F64>(P.data, lo, hi, lane);
+    const float r = proj_rate(P.scale, T);      // (T = 0: an empty row or stored zeros, y = 0 and P = b)
     // ---- phase 2
     float acc[NC];
 #pragma unroll
@@ -99,7 +60,7 @@ __global__ __launch_bounds__(256) void k_project(ProjDev P) {
 #pragma unroll
       for (int s = 0; s < PROJ_SWEEPS; s++) {
         const int jc = j[s] >= 0 ? j[s] : 0;
-        w[s] = fminf(log1pf(x[s] * r), P.cap[jc]) * P.inv_sd[jc];
+        w[s] = proj_weight(x[s], r, P.cap[jc], P.inv_sd[jc]);
       }
 #pragma unroll
       for (int s = 0; s < PROJ_SWEEPS; s++) {

@@ -2,9 +2,9 @@
 
 A query arrives as a sparse cells x genes matrix of counts.  Before it can be mapped it has to be expressed in the PCs of the reference:
 library-size normalise and log1p, scale every variable gene by the REFERENCE's mean and standard deviation, multiply by the reference's gene
-loadings.  `HarmonyLoadings` carries those three tables with the gene names; they come from whatever produced the reference's PCs (scanpy:
-``varm["PCs"]``, ``var["mean"]``, ``var["std"]``; Seurat: ``Loadings``) -- neither the PCA of the reference nor the choice of the variable
-genes is done here.  All numerics run in libharmony_mi355x.so (hmx_project_counts, include/harmony_mi355x_project.h); the zeros of the count
+loadings.  `HarmonyLoadings` carries those three tables with the gene names; they come from whatever produced the reference's PCs:
+harmony_amd.pca.fit_loadings on the reference's own counts, or another package (scanpy: ``varm["PCs"]``, ``var["mean"]``, ``var["std"]``;
+Seurat: ``Loadings``).  All numerics run in libharmony_mi355x.so (hmx_project_counts, include/harmony_mi355x_project.h); the zeros of the count
 matrix are never touched, and with ``out="device"`` the PCs stay in HBM for map_query.
 """
 import ctypes as C

@@ -3,8 +3,8 @@
  * deviation, multiply by the reference's gene loadings.  Companion of harmony_mi355x.h (handles, status codes) in the way
  * harmony_mi355x_metrics.h, harmony_mi355x_silhouette.h and harmony_mi355x_confidence.h are; the same library exports this entry point.
  *
- * The loadings, means and standard deviations come from whatever produced the reference's PCs (scanpy: varm["PCs"], var["mean"],
- * var["std"]; Seurat: Loadings); neither the PCA of the reference nor the choice of the variable genes is done here. */
+ * The loadings, means and standard deviations come from whatever produced the reference's PCs: harmony_mi355x_pca.h's operator driven by
+ * harmony_amd.pca.fit_loadings, or another package (scanpy: varm["PCs"], var["mean"], var["std"]; Seurat: Loadings). */
 #ifndef HARMONY_MI355X_PROJECT_H
 #define HARMONY_MI355X_PROJECT_H
 

@@ -142,6 +142,18 @@ if pb:
                                    ho["slabs"], ho["bytes_per_s"] / 1e9, "yes" if pb["host_equals_device_bits"] else "NO"))
 else:
     vals["PROJECT_MEASURED"] = ("**Not measured yet**: `profiles/%s_project_bench.json` (written by `tools/project_bench.py` on an MI355X) is not in the tree." % TAG)
+qb = line("pca_bench.json")      # tools/pca_bench.py
+if qb:
+    dv, ho, bd = qb["device_resident"], qb["host_resident"], qb["bound_ms"]
+    vals["PCA_MEASURED"] = ("**Measured** (`profiles/pca_bench.json`, one MI355X, %s cells x %d genes, %.0f stored counts per cell, G = %d, k = %d, %s contributing entries, "
+                            "median of %d calls by the library's timers): device-resident `gene_stats` %.1f ms (bound %.1f ms), `prepare` %.1f ms (bound %.1f ms), one `apply` %.1f ms "
+                            "(lists %.1f ms + row gathers %.1f ms if they streamed from HBM); host-resident `gene_stats` %.0f ms, `prepare` %.0f ms in %d slabs per sweep, `apply` %.1f ms; "
+                            "host- and device-resident input give the same bits: %s."
+                            % ("{:,}".format(qb["cells"]).replace(",", " "), qb["G_all"], qb["nnz_per_cell"], qb["G"], qb["k"], "{:,}".format(qb["pca_entries"]).replace(",", " "),
+                               qb["repeats"], dv["gene_stats_ms"], bd["gene_stats_device"], dv["prepare_ms"], bd["prepare_device"], dv["apply_ms"], bd["apply_lists"],
+                               bd["apply_row_gathers_from_hbm"], ho["gene_stats_ms"], ho["prepare_ms"], ho["slabs"], ho["apply_ms"], "yes" if qb["host_equals_device_bits"] else "NO"))
+else:
+    vals["PCA_MEASURED"] = "**Not measured yet**: `profiles/pca_bench.json` (written by `tools/pca_bench.py` on an MI355X) is not in the tree."
 parts = sorted(f for f in os.listdir(os.path.join(ROOT, "docs", "design_parts")) if f.endswith(".md"))
 out = io.StringIO()
 for f in parts:

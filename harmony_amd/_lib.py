@@ -100,6 +100,12 @@ PCA_SIGNATURES = {
     "hmx_pca_release": (C.c_int, [C.c_void_p]),
 }
 
+# the symbol include/harmony_mi355x_groups.h declares (gene statistics per group)
+GROUPS_SIGNATURES = {
+    "hmx_gene_stats_grouped": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, _dp,
+                                         _ip, C.c_int32, _lp, _lp, _dp, _dp, _dp]),
+}
+
 _lib = None
 
 
@@ -118,7 +124,8 @@ def load():
             "harmony_amd has no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in (list(SIGNATURES.items()) + list(METRICS_SIGNATURES.items()) + list(SILHOUETTE_SIGNATURES.items())
-                              + list(CONFIDENCE_SIGNATURES.items()) + list(PROJECT_SIGNATURES.items()) + list(PCA_SIGNATURES.items())):
+                              + list(CONFIDENCE_SIGNATURES.items()) + list(PROJECT_SIGNATURES.items()) + list(PCA_SIGNATURES.items())
+                              + list(GROUPS_SIGNATURES.items())):
         fn = getattr(lib, name)  # AttributeError if the ABI and the header drift apart
         fn.restype = res
         fn.argtypes = args

@@ -8,6 +8,7 @@
 #include "../../include/harmony_mi355x_confidence.h"  // (reference moments, mapping confidence: hmx_api_confidence.inc)
 #include "../../include/harmony_mi355x_project.h"  // (count projection: hmx_api_project.inc)
 #include "../../include/harmony_mi355x_pca.h"  // (gene statistics, the standardised matrix as an operator: hmx_api_pca.inc)
+#include "../../include/harmony_mi355x_groups.h"  // (gene statistics per group: hmx_api_groups.inc)
 #include "hmx_internal.h"
 #include "hmx_rrng.h"
 #include "hmx_plan.h"
@@ -361,3 +362,4 @@ int hmx_moe_correct_ridge(hmx_ctx* ctx) {  // src/harmony.cpp:345-638
 #include "hmx_api_confidence.inc"
 #include "hmx_api_project.inc"
 #include "hmx_api_pca.inc"
+#include "hmx_api_groups.inc"

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "hmx_group_plan.h"      // (GroupChunk: the work list of the grouped gene statistics, plain C++)
 
 namespace hmx {
 
@@ -390,6 +391,13 @@ struct PcaStatDev {
   unsigned long long* s1; unsigned long long* s2; unsigned long long* n;      // [G_all]
 };
 void l_gene_stats(const PcaStatDev& S, hipStream_t stream);
+constexpr int GROUP_CHUNK = 256;           // cells of ONE group per chunk of the grouped statistics' work list (hmx_group_plan.h): fixed, cut from the list alone
+struct GroupStatDev {
+  PcaStatDev S;                            // the rows of this launch; s1, s2, n are [B][G_all]: group b's sums of gene g at b G_all + g
+  const int* perm;                         // the kept cells sorted by group (indices into the whole matrix: row = perm[] - C.row0)
+  const GroupChunk* chunks; long long nchunks;      // this launch's chunks: their cells all lie in [C.row0, C.row0 + C.nrows)
+};
+void l_gene_stats_grouped(const GroupStatDev& Q, hipStream_t stream);
 struct PcaCompactDev {
   ProjDev C;                               // the rows of this launch (U, b, out unused)
   long long* cnt;                          // [N] count pass: contributing entries of every cell

@@ -4,6 +4,8 @@
 //                            quantised to a power-of-two step and added as 64-bit INTEGERS: a workgroup (16 waves, one cell per wave at a time) keeps the
 //                            tables of PCA_STAT_GENES genes in LDS (ds atomics), grid.y sweeps the gene ranges, and at the end every touched gene costs one
 //                            global integer add per workgroup.  Integer sums do not depend on the order: any grid, slab split or cell order gives the same bits.
+//   k_gene_stats_grouped<F64> the same sums per (group, gene): the cells arrive as chunks of one group each (hmx_group_plan.h), a workgroup's tables belong
+//                            to one group at a time and are flushed where the group changes (include/harmony_mi355x_groups.h; DESIGN "Gene statistics per group").
 //   k_pca_compact<F64, FILL> the raw CSR once to count (FILL = false) and once to fill: per cell its contributing (j, w) in CSR order (ballot prefix),
 //                            w by proj_weight -- the expression k_project uses.
 //   k_pca_hist / k_pca_scan / k_pca_place   the same entries gene-major, (cell, w) per gene in ascending cell order: a stable counting sort by gene over tiles of
@@ -18,6 +20,33 @@
 
 namespace hmx {
 
+// one cell of the gene statistics, one wave: the stored entries of row i whose gene lies in [g0, g0 + ng) into the workgroup's LDS tables
+template <bool F64>
+__device__ __forceinline__ void stat_row(const PcaStatDev& S, long long i, int lane, int g0, int ng, unsigned long long* t1, unsigned long long* t2,
+                                         unsigned* tn, unsigned& bad) {
+  const ProjDev& P = S.C;
+  long long lo = P.indptr[i] - P.base, hi = P.indptr[i + 1] - P.base;
+  if (lo < 0 || hi < lo || hi > P.nnz) { bad |= PROJ_BAD_INDPTR; lo = hi = 0; }
+  const double T = P.totals ? P.totals[P.row0 + i] : proj_row_total<F64>(P.data, lo, hi, lane);
+  const float r = proj_rate(P.scale, T);
+  for (long long e = lo + lane; e < hi; e += 64) {
+    const int col = P.indices[e];
+    const double xd = F64 ? ((const double*)P.data)[e] : (double)((const float*)P.data)[e];
+    const float x = (float)xd;
+    const bool okc = (unsigned)col < (unsigned)P.G_all;
+    const bool okx = x >= 0.f && x <= 3.0e38f;
+    if (!okc) bad |= PROJ_BAD_COLUMN;
+    if (!okx) bad |= x < 0.f ? PROJ_BAD_NEGATIVE : PROJ_BAD_NONFINITE;
+    const int g = col - g0;
+    if (okc && okx && xd > 0 && g >= 0 && g < ng) {
+      const double y = (double)fminf(proj_log(x, r), S.ymax);
+      atomicAdd(&t1[g], (unsigned long long)__double2ll_rn(y * S.q1));
+      atomicAdd(&t2[g], (unsigned long long)__double2ll_rn(y * y * S.q2));
+      atomicAdd(&tn[g], 1u);
+    }
+  }
+}
+
 template <bool F64>
 __global__ __launch_bounds__(1024) void k_gene_stats(PcaStatDev S) {
   __shared__ unsigned long long t1[PCA_STAT_GENES], t2[PCA_STAT_GENES];
@@ -28,28 +57,7 @@ __global__ __launch_bounds__(1024) void k_gene_stats(PcaStatDev S) {
   for (int g = threadIdx.x; g < ng; g += 1024) { t1[g] = 0; t2[g] = 0; tn[g] = 0; }
   __syncthreads();
   unsigned bad = 0;
-  for (long long i = (long long)blockIdx.x * 16 + wv; i < P.nrows; i += (long long)gridDim.x * 16) {
-    long long lo = P.indptr[i] - P.base, hi = P.indptr[i + 1] - P.base;
-    if (lo < 0 || hi < lo || hi > P.nnz) { bad |= PROJ_BAD_INDPTR; lo = hi = 0; }
-    const double T = P.totals ? P.totals[P.row0 + i] : proj_row_total<F64>(P.data, lo, hi, lane);
-    const float r = proj_rate(P.scale, T);
-    for (long long e = lo + lane; e < hi; e += 64) {
-      const int col = P.indices[e];
-      const double xd = F64 ? ((const double*)P.data)[e] : (double)((const float*)P.data)[e];
-      const float x = (float)xd;
-      const bool okc = (unsigned)col < (unsigned)P.G_all;
-      const bool okx = x >= 0.f && x <= 3.0e38f;
-      if (!okc) bad |= PROJ_BAD_COLUMN;
-      if (!okx) bad |= x < 0.f ? PROJ_BAD_NEGATIVE : PROJ_BAD_NONFINITE;
-      const int g = col - g0;
-      if (okc && okx && xd > 0 && g >= 0 && g < ng) {
-        const double y = (double)fminf(proj_log(x, r), S.ymax);
-        atomicAdd(&t1[g], (unsigned long long)__double2ll_rn(y * S.q1));
-        atomicAdd(&t2[g], (unsigned long long)__double2ll_rn(y * y * S.q2));
-        atomicAdd(&tn[g], 1u);
-      }
-    }
-  }
+  for (long long i = (long long)blockIdx.x * 16 + wv; i < P.nrows; i += (long long)gridDim.x * 16) stat_row<F64>(S, i, lane, g0, ng, t1, t2, tn, bad);
   __syncthreads();
   for (int g = threadIdx.x; g < ng; g += 1024)
     if (tn[g]) {
@@ -64,6 +72,59 @@ void l_gene_stats(const PcaStatDev& S, hipStream_t stream) {
   const dim3 grid((unsigned)std::min<long long>((P.nrows + 15) / 16, 256), (unsigned)((P.G_all + PCA_STAT_GENES - 1) / PCA_STAT_GENES));
   if (P.f64) hipLaunchKernelGGL((k_gene_stats<true>), grid, dim3(1024), 0, stream, S);
   else hipLaunchKernelGGL((k_gene_stats<false>), grid, dim3(1024), 0, stream, S);
+}
+
+// The same sums per (group, gene).  A workgroup walks a contiguous run of the launch's chunks (hmx_group_plan.h: <= GROUP_CHUNK cells of ONE group
+// each; the run is cut from the chunk count and the grid, the chunks themselves from the labels alone); its LDS tables belong to one group at a
+// time.  Where the group changes between two of its chunks it adds the touched genes into acc[group G_all + g] and clears them, a barrier on
+// either side (the chunk loop's bounds and every chunk's group are uniform over the workgroup).  Integer adds: the grid, the cut of the runs and
+// the order of the cells do not reach the bits.  Cost accepted: a group of a few cells touches few genes more than once, so it pays up to one
+// global atomic per stored entry -- many tiny groups are slow, never wrong.
+template <bool F64>
+__global__ __launch_bounds__(1024) void k_gene_stats_grouped(GroupStatDev Q) {
+  __shared__ unsigned long long t1[PCA_STAT_GENES], t2[PCA_STAT_GENES];
+  __shared__ unsigned tn[PCA_STAT_GENES];
+  const PcaStatDev& S = Q.S;
+  const ProjDev& P = S.C;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int g0 = blockIdx.y * PCA_STAT_GENES, ng = min(P.G_all - g0, PCA_STAT_GENES);
+  for (int g = threadIdx.x; g < ng; g += 1024) { t1[g] = 0; t2[g] = 0; tn[g] = 0; }
+  const long long c0 = Q.nchunks * blockIdx.x / gridDim.x, c1 = Q.nchunks * (blockIdx.x + 1) / gridDim.x;
+  auto flush = [&](int group) {      // between two barriers: every wave's ds atomics of `group` have landed, none of the next group has begun
+    const size_t at = (size_t)group * P.G_all + g0;
+    for (int g = threadIdx.x; g < ng; g += 1024)
+      if (tn[g]) {
+        atomicAdd(&S.s1[at + g], t1[g]); atomicAdd(&S.s2[at + g], t2[g]); atomicAdd(&S.n[at + g], (unsigned long long)tn[g]);
+        t1[g] = 0; t2[g] = 0; tn[g] = 0;
+      }
+  };
+  int cur = c0 < c1 ? Q.chunks[c0].group : 0;
+  unsigned bad = 0;
+  __syncthreads();
+  for (long long c = c0; c < c1; c++) {
+    const GroupChunk ch = Q.chunks[c];
+    if (ch.group != cur) {
+      __syncthreads();
+      flush(cur);
+      __syncthreads();
+      cur = ch.group;
+    }
+    for (int k = wv; k < ch.len; k += 16) {
+      const long long i = (long long)Q.perm[ch.start + k] - P.row0;
+      if (i >= 0 && i < P.nrows) stat_row<F64>(S, i, lane, g0, ng, t1, t2, tn, bad);      // (the plan keeps a launch's chunks inside its rows)
+    }
+  }
+  __syncthreads();
+  flush(cur);
+  if (bad) atomicOr(P.flag, bad);
+}
+
+void l_gene_stats_grouped(const GroupStatDev& Q, hipStream_t stream) {
+  const ProjDev& P = Q.S.C;
+  if (P.nrows <= 0 || Q.nchunks <= 0) return;
+  const dim3 grid((unsigned)std::min<long long>(Q.nchunks, 256), (unsigned)((P.G_all + PCA_STAT_GENES - 1) / PCA_STAT_GENES));
+  if (P.f64) hipLaunchKernelGGL((k_gene_stats_grouped<true>), grid, dim3(1024), 0, stream, Q);
+  else hipLaunchKernelGGL((k_gene_stats_grouped<false>), grid, dim3(1024), 0, stream, Q);
 }
 
 template <bool F64, bool FILL>

@@ -154,6 +154,22 @@ if qb:
                                bd["apply_row_gathers_from_hbm"], ho["gene_stats_ms"], ho["prepare_ms"], ho["slabs"], ho["apply_ms"], "yes" if qb["host_equals_device_bits"] else "NO"))
 else:
     vals["PCA_MEASURED"] = "**Not measured yet**: `profiles/pca_bench.json` (written by `tools/pca_bench.py` on an MI355X) is not in the tree."
+gb = line("group_stats_bench.json")      # tools/group_stats_bench.py
+if gb:
+    rows = []
+    for where in ("device_resident", "host_resident"):
+        r = gb.get(where)
+        if r:
+            rows.append("%s `gene_stats` %.1f ms (run-to-run spread, (max - min) / median, %.1f %% over %d calls)%s; grouped: %s"
+                        % (where.replace("_", "-"), r["gene_stats_ms"], 100.0 * r["gene_stats_spread"], len(r["gene_stats_ms_all"]),
+                           " in %d slabs" % r["slabs"] if r["slabs"] > 1 else "",
+                           ", ".join("B = %s %.1f ms (ratio %.2f)" % (b, v["ms"], v["ratio_to_gene_stats"]) for b, v in r["by_groups"].items())))
+    ok = all(v["n_cells_add_up"] for where in ("device_resident", "host_resident") if gb.get(where) for v in gb[where]["by_groups"].values())
+    vals["GROUPS_MEASURED"] = ("One MI355X, %s cells x %d genes, %.0f stored counts per cell, medians by the library's timers (the whole call): %s. The group counts add up "
+                               "to the ungrouped ones in every run: %s."
+                               % ("{:,}".format(gb["cells"]).replace(",", " "), gb["G_all"], gb["nnz_per_cell"], "; ".join(rows), "yes" if ok else "NO"))
+else:
+    vals["GROUPS_MEASURED"] = "**Not measured yet**: `profiles/group_stats_bench.json` (written by `tools/group_stats_bench.py` on an MI355X) is not in the tree."
 parts = sorted(f for f in os.listdir(os.path.join(ROOT, "docs", "design_parts")) if f.endswith(".md"))
 out = io.StringIO()
 for f in parts:

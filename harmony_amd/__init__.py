@@ -11,6 +11,7 @@ from .metrics import compute_lisi, knn, knn_predict, lisi_from_knn
 from .options import harmony_options
 from .pca import fit_loadings, gene_stats
 from .project import HarmonyLoadings, map_query_counts, project_query
+from .rank_sums import rank_sums_by_group, wilcoxon_from_rank_sums
 from .silhouette import silhouette_batch, silhouette_label, silhouette_samples
 from .ui import RunHarmony, prepare_setup_args
 from .utils import harmonize
@@ -18,4 +19,5 @@ from .utils import harmonize
 __all__ = ["RunHarmony", "harmony_options", "Harmony", "HarmonyError", "harmonize", "prepare_setup_args", "map_query",
            "HarmonyReference", "mapping_confidence", "knn", "compute_lisi", "lisi_from_knn", "knn_predict",
            "silhouette_samples", "silhouette_label", "silhouette_batch", "HarmonyLoadings", "project_query", "map_query_counts", "gene_stats", "fit_loadings",
-           "gene_stats_by_group", "variable_genes", "rank_genes_groups", "markers_from_sums"]
+           "gene_stats_by_group", "variable_genes", "rank_genes_groups", "markers_from_sums",
+           "rank_sums_by_group", "wilcoxon_from_rank_sums"]

@@ -106,6 +106,13 @@ GROUPS_SIGNATURES = {
                                          _ip, C.c_int32, _lp, _lp, _dp, _dp, _dp]),
 }
 
+# the symbol include/harmony_mi355x_ranksum.h declares (rank sums per group)
+_up = C.POINTER(C.c_uint64)
+RANKSUM_SIGNATURES = {
+    "hmx_rank_sums": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, _dp,
+                                _ip, C.c_int32, _ip, C.c_int32, _lp, _lp, _lp, _up]),
+}
+
 _lib = None
 
 
@@ -125,7 +132,7 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in (list(SIGNATURES.items()) + list(METRICS_SIGNATURES.items()) + list(SILHOUETTE_SIGNATURES.items())
                               + list(CONFIDENCE_SIGNATURES.items()) + list(PROJECT_SIGNATURES.items()) + list(PCA_SIGNATURES.items())
-                              + list(GROUPS_SIGNATURES.items())):
+                              + list(GROUPS_SIGNATURES.items()) + list(RANKSUM_SIGNATURES.items())):
         fn = getattr(lib, name)  # AttributeError if the ABI and the header drift apart
         fn.restype = res
         fn.argtypes = args

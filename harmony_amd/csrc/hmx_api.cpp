@@ -9,10 +9,13 @@
 #include "../../include/harmony_mi355x_project.h"  // (count projection: hmx_api_project.inc)
 #include "../../include/harmony_mi355x_pca.h"  // (gene statistics, the standardised matrix as an operator: hmx_api_pca.inc)
 #include "../../include/harmony_mi355x_groups.h"  // (gene statistics per group: hmx_api_groups.inc)
+#include "../../include/harmony_mi355x_ranksum.h"  // (rank sums per group: hmx_api_ranksum.inc)
 #include "hmx_internal.h"
 #include "hmx_rrng.h"
 #include "hmx_plan.h"
 #include "hmx_round.h"
+#include "hmx_ranksum.h"
+#include "hmx_ranksum_plan.h"
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>
@@ -363,3 +366,4 @@ int hmx_moe_correct_ridge(hmx_ctx* ctx) {  // src/harmony.cpp:345-638
 #include "hmx_api_project.inc"
 #include "hmx_api_pca.inc"
 #include "hmx_api_groups.inc"
+#include "hmx_api_ranksum.inc"

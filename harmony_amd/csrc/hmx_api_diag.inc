@@ -172,6 +172,9 @@ int64_t hmx_get(hmx_ctx* ctx, const char* field, double* out, int64_t cap) {
   if (f == "sold_carry") return scalar(ctx->carry_ok ? 1.0 : 0.0);
   if (f == "project_slabs") return scalar((double)ctx->project_slabs);
   if (f == "pca_entries") return scalar((double)ctx->pca_entries);
+  if (f == "ranksum_blocks") return scalar((double)ctx->ranksum_blocks);      // the gene blocks (fill sweeps) of the last hmx_rank_sums
+  if (f == "ranksum_sort_lds") return scalar((double)RS_SORT_LDS);            // ... the longest list it sorts in LDS, the chunk of its radix sort and rank scans
+  if (f == "ranksum_chunk") return scalar((double)RS_CHUNK);
   if (f == "carried_rounds") return scalar((double)ctx->carried_rounds);
   if (f == "rounds_without_R") return scalar((double)ctx->rounds_without_R);
   if (f == "chain_rounds") return scalar((double)ctx->chain_rounds);

@@ -165,6 +165,7 @@ int hmx_set_int(hmx_ctx* ctx, const char* field, int64_t v) {
   else if (f == "seq_strict") { ctx->seq_strict = v != 0; if (v && ctx->seq_max_passes < 64) ctx->seq_max_passes = 64; }
   else if (f == "seq_max_passes") { if (v < 2 || v > 256) return fail(ctx, HMX_ERR_ARG, "seq_max_passes: 2..256"); ctx->seq_max_passes = (int)v; }
   else if (f == "project_slab_bytes") { if (v < 0) return fail(ctx, HMX_ERR_ARG, "project_slab_bytes: 0 (the default) or a positive byte count"); ctx->project_slab_bytes = v; }
+  else if (f == "ranksum_list_bytes") { if (v < 0) return fail(ctx, HMX_ERR_ARG, "ranksum_list_bytes: 0 (the default) or a positive byte count"); ctx->ranksum_list_bytes = v; }
   else if (f == "device") ctx->device = (int)v;
   else if (f == "profile") { ctx->profile = (int)(v < 0 ? 0 : v > 2 ? 2 : v); ctx->prof_update_ms = 0; ctx->prof_update_launches = 0; ctx->prof_update_cells = 0; ctx->prof_update_steps = 0; ctx->ev_used = 0;
                              ctx->ph_used = 0; ctx->gpu_timers.clear(); }

@@ -7,8 +7,8 @@ for fit_loadings(genes_use=genes[idx]).  After knn_predict or a clustering the s
 `rank_genes_groups` is Welch's t-test on the log-normalised expression, scanpy's default.  Both rest on one primitive, per (group, gene) the
 number of expressing cells and the sums of y and y^2, y = log1p(x scale / T): hmx_gene_stats_grouped (include/harmony_mi355x_groups.h), whose
 fixed-point sums partition hmx_gene_stats' exactly.  Everything after the sums is fp64 NumPy here: `select_variable_genes` and
-`markers_from_sums` are pure functions of the sums.  Seurat's vst, scanpy's binned dispersion, rank-sum tests and p-values are not implemented
-(the caller has `score` and `df`).
+`markers_from_sums` are pure functions of the sums.  The Wilcoxon rank-sum test needs ranks, not sums: rank_genes_groups(method="wilcoxon") takes
+them from rank_sums.py (hmx_rank_sums).  Seurat's vst, scanpy's binned dispersion and p-values are not implemented (the caller has `score` and `df`).
 """
 import ctypes as C
 
@@ -181,11 +181,18 @@ def markers_from_sums(n_obs, n_cells, s1, s2, reference="rest", step=None):
     return dict(mean_in=m1, mean_out=m2, pct_in=pct_in, pct_out=pct_out, logfoldchange=lfc, score=score, df=df, order=order)
 
 
-def rank_genes_groups(counts, genes, groups, levels=None, reference="rest", scale=1e4, totals=None, device=None, _handle=None):
+def rank_genes_groups(counts, genes, groups, levels=None, reference="rest", scale=1e4, totals=None, device=None, _handle=None, method="t-test"):
     """The genes that mark each group: Welch's t-test on the log-normalised expression (scanpy's default rank_genes_groups) of every level
     against all other cells of the levels (reference="rest") or against one level.  groups, levels: as for gene_stats_by_group (cells of no level
-    are left out of "rest" too).  -> markers_from_sums' dict with `levels` and `n_obs`: order[b, 0] is the gene that marks level b most."""
+    are left out of "rest" too).  -> markers_from_sums' dict with `levels` and `n_obs`: order[b, 0] is the gene that marks level b most.
+    method="wilcoxon": the Wilcoxon rank-sum test instead (Seurat's and presto's default): `score`, `order` and the new `auc`, `u` come from the
+    exact rank sums (rank_sums.wilcoxon_from_rank_sums; the integers `n_pos`, `rank2`, `tie3` are returned with them, `df` is not), while mean_*,
+    pct_* and logfoldchange still come from gene_stats_by_group on the same handle.  Cost: one count sweep and one sweep per gene block on top of
+    the t-test's single sweep; with reference=<level> the two groups' cells alone are ranked, ONE library call per other level (B - 1 calls,
+    each of them sweeping the whole matrix), so prefer "rest" for many levels."""
     what = "rank_genes_groups"
+    if method not in ("t-test", "wilcoxon"):
+        raise ValueError("%s: method must be 't-test' or 'wilcoxon'" % what)
     codes, lv = _codes(groups, levels, what)
     ref = "rest"
     if not (isinstance(reference, str) and reference == "rest"):
@@ -193,7 +200,17 @@ def rank_genes_groups(counts, genes, groups, levels=None, reference="rest", scal
         if at.size != 1:
             raise ValueError("%s: reference must be 'rest' or one of the levels, got %r" % (what, reference))
         ref = int(at[0])
-    gs = gene_stats_by_group(counts, genes, groups, levels=levels, scale=scale, totals=totals, device=device, _handle=_handle)
-    out = markers_from_sums(gs["n_obs"], gs["n_cells"], gs["s1"], gs["s2"], reference=ref, step=gs["step"])
-    out["levels"], out["n_obs"] = gs["levels"], gs["n_obs"]
+    if method == "wilcoxon":
+        from .rank_sums import one_handle, wilcoxon_markers
+        _handle, owner = one_handle(device, _handle)
+    try:
+        gs = gene_stats_by_group(counts, genes, groups, levels=levels, scale=scale, totals=totals, device=device, _handle=_handle)
+        out = markers_from_sums(gs["n_obs"], gs["n_cells"], gs["s1"], gs["s2"], reference=ref, step=gs["step"])
+        out["levels"], out["n_obs"] = gs["levels"], gs["n_obs"]
+        if method == "wilcoxon":
+            del out["df"]
+            out.update(wilcoxon_markers(counts, genes, groups, levels, ref, scale, totals, device, _handle))
+    finally:
+        if method == "wilcoxon" and owner is not None:
+            owner.__exit__()
     return out

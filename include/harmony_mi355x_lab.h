@@ -23,6 +23,8 @@ extern "C" {
  *   fields "grid", "upd_wps" (before setup), "upd_tpw", "comm_force";
  *   "project_slab_bytes" (hmx_project_counts with a host-resident matrix: index + value bytes of a staging slab, 0 = the default 256 MiB; the
  *   result does not depend on it, bit for bit; hmx_get "project_slabs": the slabs the last such call ran);
+ *   "ranksum_list_bytes" (the rank sums of harmony_mi355x_ranksum.h: bytes of a gene block's list and sort buffer, 0 = the default 8 GiB; the
+ *   result does not depend on it, bit for bit; hmx_get "ranksum_blocks": the gene blocks the last such call ran);
  *   environment, read by hmx_setup: HMX_GRID, HMX_NREP, HMX_UPD_WPS (2|4), HMX_USIG=0 (general-sigma kernels),
  *   HMX_UPD_THREADS, HMX_UPD_MAXBLOCKS, HMX_STATIC_MAXBLOCKS, HMX_UPD_TPW, HMX_FUSED_FOLD=0, HMX_FOLD_IMPL=split|merged,
  *   HMX_OLDSUM_IMPL=gather|stream1, HMX_MOE_IMPL=v1 (first-generation kernels),

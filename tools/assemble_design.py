@@ -170,6 +170,42 @@ if gb:
                                % ("{:,}".format(gb["cells"]).replace(",", " "), gb["G_all"], gb["nnz_per_cell"], "; ".join(rows), "yes" if ok else "NO"))
 else:
     vals["GROUPS_MEASURED"] = "**Not measured yet**: `profiles/group_stats_bench.json` (written by `tools/group_stats_bench.py` on an MI355X) is not in the tree."
+rb = line("ranksum_bench.json")      # tools/ranksum_bench.py
+if rb:
+    rows = []
+    for where in ("device_resident", "host_resident"):
+        r = rb.get(where)
+        if r:
+            rows.append("%s `rank_sums` %.0f ms (spread, (max - min) / median, %.1f %% over %d calls) in %d gene block%s%s: count sweep %.0f ms, fill sweeps %.0f ms, "
+                        "sort and rank %.0f ms; `gene_stats_by_group` beside it %.1f ms (spread %.1f %%), ratio %.1f; %s list entries, %s of them on the radix path: "
+                        "the byte bound of the lists is %.1f ms"
+                        % (where.replace("_", "-"), r["ms"], 100.0 * r["spread"], len(r["ms_all"]), r["gene_blocks"], "" if r["gene_blocks"] == 1 else "s",
+                           ", %d slabs per sweep" % r["slabs"] if r["slabs"] > 1 else "", r["count_ms"], r["fill_ms"], r["sort_ms"], r["gene_stats_grouped_ms"],
+                           100.0 * r["gene_stats_grouped_spread"], r["ratio_to_gene_stats_grouped"], "{:,}".format(r["entries"]).replace(",", " "),
+                           "{:,}".format(r["entries_on_the_radix_path"]).replace(",", " "), r["bound_ms_list_bytes"]))
+    ok = all(rb[w]["n_pos_equals_n_cells"] and rb[w]["rank_sums_add_up"] and rb[w].get("same_integers_as_the_first_residence", True)
+             for w in ("device_resident", "host_resident") if rb.get(w))
+    cpu = rb.get("cpu_scipy_spec")
+    vals["RANKSUM_MEASURED"] = ("**Measured** (`profiles/ranksum_bench.json`, one MI355X, %s cells x %d genes, %.0f stored counts per cell, B = %d, medians by the library's "
+                                "timers): %s. The positive counts equal `gene_stats_by_group`'s, the rank sums add up to N(N + 1) and both residences give the same "
+                                "integers: %s. CPU yardstick, as measured and not extrapolated: %s."
+                                % ("{:,}".format(rb["cells"]).replace(",", " "), rb["G_all"], rb["nnz_per_cell"], rb["groups"], "; ".join(rows), "yes" if ok else "NO",
+                                   "the scipy spec takes %.0f s on %s cells x %d genes" % (cpu["seconds"], "{:,}".format(cpu["cells"]).replace(",", " "), cpu["genes"])
+                                   if cpu else "scipy did not import"))
+    try:      # the kernel trace of the device-resident call (rocprofv3 --kernel-trace --stats, a run of its own)
+        import csv
+        tot = {}
+        for row in csv.DictReader(open(os.path.join(P, "ranksum_kernel_stats.csv"))):
+            name = row["Name"].replace("void ", "").replace("hmx::", "").split("(")[0]
+            tot[name] = tot.get(name, 0.0) + float(row["TotalDurationNs"]) / 1e6
+        vals["RANKSUM_FILL_KERNEL_MS"] = fmt(sum(v for k, v in tot.items() if k.startswith("k_rank_sweep<") and k.endswith(", true>")))
+        vals["RANKSUM_COUNT_KERNEL_MS"] = fmt(sum(v for k, v in tot.items() if k.startswith("k_rank_sweep<") and k.endswith(", false>")))
+        vals["RANKSUM_SORT_KERNEL_MS"] = fmt(tot.get("k_rank_sort", 0.0))
+        vals["RANKSUM_GROUPED_KERNEL_MS"] = fmt(sum(v for k, v in tot.items() if k.startswith("k_gene_stats_grouped")))
+    except Exception:
+        missing.append("ranksum_kernel_stats.csv")
+else:
+    vals["RANKSUM_MEASURED"] = "**Not measured yet**: `profiles/ranksum_bench.json` (written by `tools/ranksum_bench.py` on an MI355X) is not in the tree."
 parts = sorted(f for f in os.listdir(os.path.join(ROOT, "docs", "design_parts")) if f.endswith(".md"))
 out = io.StringIO()
 for f in parts:

@@ -4,6 +4,7 @@ Host-side mirror of the reference's R API (RunHarmony / harmony_options / the `h
 object) over the C ABI in include/harmony_mi355x.h.  All numerics run in hand-written HIP
 (harmony_amd/csrc); there is no CPU fallback.
 """
+from .graph import connected_components, graph_connectivity, graph_from_knn, neighbors
 from .group_stats import gene_stats_by_group, markers_from_sums, rank_genes_groups, variable_genes
 from .harmony_obj import Harmony, HarmonyError
 from .mapping import HarmonyReference, map_query, mapping_confidence
@@ -20,4 +21,4 @@ __all__ = ["RunHarmony", "harmony_options", "Harmony", "HarmonyError", "harmoniz
            "HarmonyReference", "mapping_confidence", "knn", "compute_lisi", "lisi_from_knn", "knn_predict",
            "silhouette_samples", "silhouette_label", "silhouette_batch", "HarmonyLoadings", "project_query", "map_query_counts", "gene_stats", "fit_loadings",
            "gene_stats_by_group", "variable_genes", "rank_genes_groups", "markers_from_sums",
-           "rank_sums_by_group", "wilcoxon_from_rank_sums"]
+           "rank_sums_by_group", "wilcoxon_from_rank_sums", "neighbors", "graph_from_knn", "connected_components", "graph_connectivity"]

@@ -113,6 +113,14 @@ RANKSUM_SIGNATURES = {
                                 _ip, C.c_int32, _ip, C.c_int32, _lp, _lp, _lp, _up]),
 }
 
+# the symbols include/harmony_mi355x_graph.h declares (the neighbour graph, connected components)
+GRAPH_SIGNATURES = {
+    "hmx_graph_from_knn": (C.c_int, [C.c_void_p, _ip, _fp, C.c_int64, C.c_int32, _lp, _ip, _fp, C.c_int64, _dp, _dp]),
+    "hmx_neighbor_graph": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _ip, _fp,
+                                     _lp, _ip, _fp, C.c_int64, _dp, _dp]),
+    "hmx_graph_components": (C.c_int, [C.c_void_p, C.c_int64, _lp, _ip, _ip, _ip, _lp]),
+}
+
 _lib = None
 
 
@@ -132,7 +140,7 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in (list(SIGNATURES.items()) + list(METRICS_SIGNATURES.items()) + list(SILHOUETTE_SIGNATURES.items())
                               + list(CONFIDENCE_SIGNATURES.items()) + list(PROJECT_SIGNATURES.items()) + list(PCA_SIGNATURES.items())
-                              + list(GROUPS_SIGNATURES.items()) + list(RANKSUM_SIGNATURES.items())):
+                              + list(GROUPS_SIGNATURES.items()) + list(RANKSUM_SIGNATURES.items()) + list(GRAPH_SIGNATURES.items())):
         fn = getattr(lib, name)  # AttributeError if the ABI and the header drift apart
         fn.restype = res
         fn.argtypes = args

@@ -10,12 +10,14 @@
 #include "../../include/harmony_mi355x_pca.h"  // (gene statistics, the standardised matrix as an operator: hmx_api_pca.inc)
 #include "../../include/harmony_mi355x_groups.h"  // (gene statistics per group: hmx_api_groups.inc)
 #include "../../include/harmony_mi355x_ranksum.h"  // (rank sums per group: hmx_api_ranksum.inc)
+#include "../../include/harmony_mi355x_graph.h"  // (the neighbour graph and its components: hmx_api_graph.inc)
 #include "hmx_internal.h"
 #include "hmx_rrng.h"
 #include "hmx_plan.h"
 #include "hmx_round.h"
 #include "hmx_ranksum.h"
 #include "hmx_ranksum_plan.h"
+#include "hmx_graph.h"
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>
@@ -367,3 +369,4 @@ int hmx_moe_correct_ridge(hmx_ctx* ctx) {  // src/harmony.cpp:345-638
 #include "hmx_api_pca.inc"
 #include "hmx_api_groups.inc"
 #include "hmx_api_ranksum.inc"
+#include "hmx_api_graph.inc"

@@ -175,6 +175,7 @@ int64_t hmx_get(hmx_ctx* ctx, const char* field, double* out, int64_t cap) {
   if (f == "ranksum_blocks") return scalar((double)ctx->ranksum_blocks);      // the gene blocks (fill sweeps) of the last hmx_rank_sums
   if (f == "ranksum_sort_lds") return scalar((double)RS_SORT_LDS);            // ... the longest list it sorts in LDS, the chunk of its radix sort and rank scans
   if (f == "ranksum_chunk") return scalar((double)RS_CHUNK);
+  if (f == "graph:cc_rounds") return scalar((double)ctx->graph_cc_rounds);      // the hook-and-jump rounds of the last hmx_graph_components
   if (f == "carried_rounds") return scalar((double)ctx->carried_rounds);
   if (f == "rounds_without_R") return scalar((double)ctx->rounds_without_R);
   if (f == "chain_rounds") return scalar((double)ctx->chain_rounds);

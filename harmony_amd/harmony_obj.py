@@ -318,6 +318,12 @@ class Harmony(object):
         from .metrics import harmony_lisi
         return harmony_lisi(self, meta_data, label_colnames, perplexity)
 
+    def neighbors(self, n_neighbors=15, prune_zeros=True):
+        """The neighbour graph (graph.neighbors) of the handle's current Z_corr: (distances, connectivities) as scipy.sparse.csr_matrix, rows in
+        the order the cells were given in.  Z_corr is read where it lives in HBM; no host round trip."""
+        from .graph import harmony_neighbors
+        return harmony_neighbors(self, n_neighbors, prune_zeros)
+
     def silhouette(self, meta_data, label_col, group_col=None, return_ab=False):
         """Silhouette widths (silhouette.silhouette_samples) of the handle's current Z_corr over the column `label_col` of meta_data, within the
         levels of `group_col` when one is named; one label per cell in the order the cells were given in.  Returns s, or (s, a, b).  Z_corr

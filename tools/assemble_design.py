@@ -206,6 +206,31 @@ if rb:
         missing.append("ranksum_kernel_stats.csv")
 else:
     vals["RANKSUM_MEASURED"] = "**Not measured yet**: `profiles/ranksum_bench.json` (written by `tools/ranksum_bench.py` on an MI355X) is not in the tree."
+gr = line("graph_bench.json")      # tools/graph_bench.py
+if gr:
+    rows = []
+    for r in gr["runs"]:
+        rows.append("`n_neighbors` = %d: kNN %.0f ms, graph stage %.1f ms (spread %.1f %% over %d calls) = %.1f %% of the kNN in front of it, %s entries, largest "
+                    "in-degree %d; byte bound %.2f ms, so the stage runs at %.1f %% of it; components within labels %.1f ms (%d components, %d within labels, graph "
+                    "connectivity %.4f); the same bits in every call: %s"
+                    % (r["n_neighbors"], r["knn_ms"], r["graph_ms"], 100.0 * r["graph_spread"], len(r["graph_ms_all"]), 100.0 * r["graph_share_of_knn"],
+                       "{:,}".format(r["entries"]).replace(",", " "), r["max_in_degree"], r["bound_ms_bytes"], 100.0 * r["share_of_bound"],
+                       r["components_within_labels_ms"], r["components"], r["components_within_labels"], r["graph_connectivity"],
+                       "yes" if r["same_bits_every_call"] else "NO"))
+    vals["GRAPH_MEASURED"] = ("**Measured** (`profiles/graph_bench.json`, one MI355X, %s cells x %d PCs, float32 on the host, medians by the library's timers): %s."
+                              % ("{:,}".format(gr["cells"]).replace(",", " "), gr["d"], "; ".join(rows)))
+    try:      # the kernel table of the n_neighbors = 15 calls (rocprofv3 --kernel-trace --stats, a run of its own)
+        import csv
+        ks = []
+        for row in csv.DictReader(open(os.path.join(P, "graph_kernel_stats.csv"))):
+            name = row["Name"].replace("void ", "").replace("hmx::", "").split("(")[0]
+            if name.startswith(("k_graph_", "k_smooth_knn", "k_scan_", "k_cc_")):
+                ks.append((float(row["AverageNs"]) / 1e6, int(row["Calls"]), name))
+        vals["GRAPH_KERNELS"] = "; ".join("`%s` %.3f ms x %d" % (n, ms, c) for ms, c, n in sorted(ks, reverse=True))
+    except Exception:
+        missing.append("graph_kernel_stats.csv")
+else:
+    vals["GRAPH_MEASURED"] = "**Not measured yet**: `profiles/graph_bench.json` (written by `tools/graph_bench.py` on an MI355X) is not in the tree."
 parts = sorted(f for f in os.listdir(os.path.join(ROOT, "docs", "design_parts")) if f.endswith(".md"))
 out = io.StringIO()
 for f in parts:

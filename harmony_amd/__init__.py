@@ -14,6 +14,7 @@ from .pca import fit_loadings, gene_stats
 from .project import HarmonyLoadings, map_query_counts, project_query
 from .rank_sums import rank_sums_by_group, wilcoxon_from_rank_sums
 from .silhouette import silhouette_batch, silhouette_label, silhouette_samples
+from .snn import snn, snn_from_knn
 from .ui import RunHarmony, prepare_setup_args
 from .utils import harmonize
 
@@ -21,4 +22,5 @@ __all__ = ["RunHarmony", "harmony_options", "Harmony", "HarmonyError", "harmoniz
            "HarmonyReference", "mapping_confidence", "knn", "compute_lisi", "lisi_from_knn", "knn_predict",
            "silhouette_samples", "silhouette_label", "silhouette_batch", "HarmonyLoadings", "project_query", "map_query_counts", "gene_stats", "fit_loadings",
            "gene_stats_by_group", "variable_genes", "rank_genes_groups", "markers_from_sums",
-           "rank_sums_by_group", "wilcoxon_from_rank_sums", "neighbors", "graph_from_knn", "connected_components", "graph_connectivity"]
+           "rank_sums_by_group", "wilcoxon_from_rank_sums", "neighbors", "graph_from_knn", "connected_components", "graph_connectivity",
+           "snn", "snn_from_knn"]

@@ -121,6 +121,13 @@ GRAPH_SIGNATURES = {
     "hmx_graph_components": (C.c_int, [C.c_void_p, C.c_int64, _lp, _ip, _ip, _ip, _lp]),
 }
 
+# the symbols include/harmony_mi355x_snn.h declares (Seurat's shared-nearest-neighbour graph)
+SNN_SIGNATURES = {
+    "hmx_snn_from_knn": (C.c_int, [C.c_void_p, _ip, C.c_int64, C.c_int32, C.c_double, _lp, _ip, _fp, C.c_int64]),
+    "hmx_snn_graph": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_double, _ip, _fp,
+                                _lp, _ip, _fp, C.c_int64]),
+}
+
 _lib = None
 
 
@@ -140,7 +147,8 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in (list(SIGNATURES.items()) + list(METRICS_SIGNATURES.items()) + list(SILHOUETTE_SIGNATURES.items())
                               + list(CONFIDENCE_SIGNATURES.items()) + list(PROJECT_SIGNATURES.items()) + list(PCA_SIGNATURES.items())
-                              + list(GROUPS_SIGNATURES.items()) + list(RANKSUM_SIGNATURES.items()) + list(GRAPH_SIGNATURES.items())):
+                              + list(GROUPS_SIGNATURES.items()) + list(RANKSUM_SIGNATURES.items()) + list(GRAPH_SIGNATURES.items())
+                              + list(SNN_SIGNATURES.items())):
         fn = getattr(lib, name)  # AttributeError if the ABI and the header drift apart
         fn.restype = res
         fn.argtypes = args

@@ -11,6 +11,7 @@
 #include "../../include/harmony_mi355x_groups.h"  // (gene statistics per group: hmx_api_groups.inc)
 #include "../../include/harmony_mi355x_ranksum.h"  // (rank sums per group: hmx_api_ranksum.inc)
 #include "../../include/harmony_mi355x_graph.h"  // (the neighbour graph and its components: hmx_api_graph.inc)
+#include "../../include/harmony_mi355x_snn.h"  // (Seurat's shared-nearest-neighbour graph: hmx_api_snn.inc)
 #include "hmx_internal.h"
 #include "hmx_rrng.h"
 #include "hmx_plan.h"
@@ -370,3 +371,4 @@ int hmx_moe_correct_ridge(hmx_ctx* ctx) {  // src/harmony.cpp:345-638
 #include "hmx_api_groups.inc"
 #include "hmx_api_ranksum.inc"
 #include "hmx_api_graph.inc"
+#include "hmx_api_snn.inc"

@@ -176,6 +176,10 @@ int64_t hmx_get(hmx_ctx* ctx, const char* field, double* out, int64_t cap) {
   if (f == "ranksum_sort_lds") return scalar((double)RS_SORT_LDS);            // ... the longest list it sorts in LDS, the chunk of its radix sort and rank scans
   if (f == "ranksum_chunk") return scalar((double)RS_CHUNK);
   if (f == "graph:cc_rounds") return scalar((double)ctx->graph_cc_rounds);      // the hook-and-jump rounds of the last hmx_graph_components
+  if (f == "snn:s_min") return scalar((double)ctx->snn_s_min);      // the last SNN call: an entry was kept iff its shared count reached this
+  if (f == "snn:long_rows") return scalar((double)ctx->snn_long_rows);      // ... and the rows that took the windowed path
+  if (f == "snn:short_cap") return scalar((double)SNN_SHORT_CAP);      // the largest candidate count one wave sorts in LDS; the cells of the long path's window
+  if (f == "snn:window") return scalar((double)SNN_WINDOW);
   if (f == "carried_rounds") return scalar((double)ctx->carried_rounds);
   if (f == "rounds_without_R") return scalar((double)ctx->rounds_without_R);
   if (f == "chain_rounds") return scalar((double)ctx->chain_rounds);

@@ -261,6 +261,8 @@ struct hmx_ctx {
   int64_t ranksum_list_bytes = 0, ranksum_blocks = 0;
   // ---- connected components (hmx_graph_components): the hook-and-jump rounds of the last call ("graph:cc_rounds")
   int64_t graph_cc_rounds = 0;
+  // ---- the SNN graph (hmx_snn_from_knn / hmx_snn_graph): the pruning threshold and the long rows of the last call ("snn:s_min", "snn:long_rows")
+  int64_t snn_s_min = 0, snn_long_rows = 0;
   // ---- the reference's PCA (hmx_pca_prepare / apply / release, hmx_api_pca.inc): the prepared lists (a PcaState) and their entry count
   std::shared_ptr<void> pca; int64_t pca_entries = 0;
   QueryDev qd{};            // the query's device tables (rows in D.Zo / D.Zc, internal order in D.perm / D.invperm)

@@ -1,5 +1,6 @@
 // hmx_graph.h -- what hmx_graph.hip (the kernels) and hmx_api_graph.inc (the host's orchestration) share: the constants, the argument struct and
-// the launchers of the neighbour graph and its connected components (include/harmony_mi355x_graph.h; DESIGN "The neighbour graph").
+// the launchers of the neighbour graph and its connected components (include/harmony_mi355x_graph.h; DESIGN "The neighbour graph"), and of
+// Seurat's SNN graph over the same transposed lists (hmx_api_snn.inc; include/harmony_mi355x_snn.h; DESIGN "Seurat's SNN graph").
 #pragma once
 #include "hmx_internal.h"
 
@@ -35,6 +36,25 @@ void l_graph_scan(const Launch& L, const unsigned* cnt, long long n, long long* 
 void l_graph_place(const Launch& L, const GraphDev& G);
 void l_graph_sort(const Launch& L, const GraphDev& G);
 void l_graph_union(const Launch& L, const GraphDev& G, bool write);
+
+// ---- Seurat's shared-nearest-neighbour graph (include/harmony_mi355x_snn.h; DESIGN "Seurat's SNN graph") ---------------------------------------------
+constexpr int SNN_SHORT_CAP = 2048;        // candidates (with multiplicity) one wave sorts in LDS: a row up to this count takes the short path
+constexpr int SNN_WINDOW = 8192;           // cells of the long path's dense window: one 8-bit counter each, four to an LDS word
+constexpr int SNN_LONG_WGS = 1024;         // workgroups that share the long rows
+constexpr int SNN_MAX_K = 129;             // the cell itself and at most 128 neighbours
+
+struct SnnDev {
+  const int* idx; long long N; int m;                         // the neighbour lists [N][m], self excluded; the sets N+(i) add the cell itself
+  const long long* toff; const unsigned long long* tkey;      // the transposed lists of hmx_graph.hip: offsets [N + 1], source * m + slot ascending per row
+  int s_min; const float* jtab;                               // an entry is kept iff its shared count s >= s_min; jtab [m + 2]: the weight of s
+  unsigned* cand;                                             // [N] candidates with multiplicity C_i (saturated at 2^32 - 1)
+  int* longrows; unsigned* nlong;                             // the rows with C_i > SNN_SHORT_CAP
+  unsigned* len; const long long* indptr; int* indices; float* weights;      // row lengths, then (indptr scanned) the CSR
+};
+void l_snn_indegree(const Launch& L, const GraphDev& G);      // deg[j] += 1 per valid slot (what k_smooth_knn counts beside its search)
+void l_snn_rowweight(const Launch& L, const SnnDev& S);
+void l_snn_short(const Launch& L, const SnnDev& S, bool write);
+void l_snn_long(const Launch& L, const SnnDev& S, bool write);
 
 struct CcDev {
   long long N; const long long* indptr; const int* indices; const int* labels;      // a symmetric CSR pattern, rows ascending; labels [N] or nullptr

@@ -10,6 +10,9 @@
 //   k_graph_sort_long     one workgroup per long row: 128-entry chunks by the same rank sort, then merge passes between two buffers;
 //   k_graph_union<WRITE>  one wave per row: the out-list sorted by index in LDS, merged with the sorted in-list by ranks (binary searches);
 //                         WRITE = false counts the row's length, WRITE = true writes indices / weights behind the scanned lengths;
+//   k_snn_indegree / rowweight / short<WRITE> / long<WRITE>   Seurat's SNN graph (include/harmony_mi355x_snn.h; DESIGN "Seurat's SNN graph") over the
+//                         same transposed lists: in-degrees alone, candidates per row, one wave sorting a row's candidates in LDS, one workgroup
+//                         walking a long row's index range in dense windows of 8-bit counters;
 //   k_cc_check / init / hook / jump   components: the pattern's checks, comp[i] = i, the hooks (integer atomicMin), bounded pointer jumping.
 // Integer atomics only; every floating-point sum has a fixed order; after the segment sort nothing depends on the order of placement.
 #include "hmx_graph.h"
@@ -304,6 +307,220 @@ __global__ __launch_bounds__(256) void k_graph_union(GraphDev G) {
   }
 }
 
+// ---- Seurat's shared-nearest-neighbour graph -----------------------------------------------------------------------------------------------------
+// s_il = |N+(i) & N+(l)| is the multiplicity of l among the candidates of row i: for every j in N+(i), the sources that list j and j itself.
+// Integers throughout: the weight of s is looked up in S.jtab.
+__global__ __launch_bounds__(256) void k_snn_indegree(GraphDev G) {
+  const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (p >= G.N * G.m) return;
+  const int j = G.idx[p];
+  if (j >= 0 && j < G.N) atomicAdd(G.deg + j, 1u);
+}
+__device__ __forceinline__ int snn_source(u64 key, int m) {
+  return (key >> 32) == 0 ? (int)((unsigned)key / (unsigned)m) : (int)(key / (u64)m);
+}
+// entry q of N+(i): the list's slot q, then the cell itself; -1: an unfilled slot
+__device__ __forceinline__ int snn_entry(const SnnDev& S, long long i, int q) {
+  return q < S.m ? S.idx[(size_t)i * S.m + q] : q == S.m ? (int)i : -1;
+}
+__device__ __forceinline__ int wave_inclusive(int v, int l) {
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const int o = __shfl_up(v, d, 64);
+    if (l >= d) v += o;
+  }
+  return v;
+}
+
+__global__ __launch_bounds__(256) void k_snn_rowweight(SnnDev S) {
+  const int l = threadIdx.x & 63;
+  const long long i = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= S.N) return;
+  long long c = 0;
+  for (int q = l; q <= S.m; q += 64) {
+    const int j = snn_entry(S, i, q);
+    if (j >= 0) c += S.toff[j + 1] - S.toff[j] + 1;
+  }
+  c = wave_sum(c);
+  if (l == 0) {
+    S.cand[i] = (unsigned)min(c, 0xffffffffll);
+    if (c > SNN_SHORT_CAP) {
+      const unsigned at = atomicAdd(S.nlong, 1u);
+      if ((long long)at < S.N) S.longrows[at] = (int)i;
+    }
+  }
+}
+
+// the bitonic sort of P = 128 IT keys in LDS by one wave (IT = 0: 64 keys, half the lanes).  IT is a template argument so that a step's
+// compare-exchanges unroll: a lane issues all its reads before its first write instead of one dependent read-write pair after the other
+template <int IT>
+__device__ __forceinline__ void snn_bitonic(unsigned* sc, int l) {
+  constexpr int PER = IT > 0 ? IT : 1, P = IT > 0 ? 128 * IT : 64;
+  const bool on = IT > 0 || l < 32;
+  for (int k2 = 2; k2 <= P; k2 <<= 1)
+    for (int j2 = k2 >> 1; j2 > 0; j2 >>= 1) {
+      int a[PER];
+      unsigned x[PER], y[PER];
+#pragma unroll
+      for (int u = 0; u < PER; u++) {
+        const int t = l + 64 * u;
+        a[u] = ((t & ~(j2 - 1)) << 1) | (t & (j2 - 1));
+        x[u] = on ? sc[a[u]] : 0u;
+        y[u] = on ? sc[a[u] | j2] : 0u;
+      }
+#pragma unroll
+      for (int u = 0; u < PER; u++)
+        if (on && (x[u] > y[u]) == ((a[u] & k2) == 0)) { sc[a[u]] = y[u]; sc[a[u] | j2] = x[u]; }
+      __syncthreads();
+    }
+}
+
+// one wave per row of at most SNN_SHORT_CAP candidates: gathered into LDS, sorted (bitonic), run lengths, the survivors placed by ballot prefixes
+template <bool WRITE>
+__global__ __launch_bounds__(64) void k_snn_short(SnnDev S) {
+  constexpr int SLOTS = 192;                             // three entries of N+(i) per lane
+  __shared__ unsigned sc[SNN_SHORT_CAP];
+  __shared__ long long eb[SLOTS];
+  __shared__ int en[SLOTS], eo[SLOTS], ej[SLOTS];
+  const int l = threadIdx.x, m = S.m;
+  const long long i = blockIdx.x;
+  if (i >= S.N || S.cand[i] > (unsigned)SNN_SHORT_CAP) return;      // (the whole workgroup: a long row)
+  int run = 0;
+#pragma unroll
+  for (int s = 0; s < 3; s++) {
+    const int q = l + 64 * s;
+    const int j = snn_entry(S, i, q);
+    long long b = 0;
+    int cnt = 0;
+    if (j >= 0) { b = S.toff[j]; cnt = (int)(S.toff[j + 1] - b) + 1; }
+    const int inc = wave_inclusive(cnt, l);
+    eb[q] = b; en[q] = cnt; eo[q] = run + inc - cnt; ej[q] = j;
+    run += __shfl(inc, 63, 64);
+  }
+  const int n = min(run, SNN_SHORT_CAP);
+  __syncthreads();
+  for (int q = 0; q <= m; q++) {
+    const int cnt = en[q], o = eo[q];
+    const u64* keys = S.tkey + eb[q];
+    for (int t = l; t < cnt; t += 64) {
+      const unsigned v = t < cnt - 1 ? (unsigned)snn_source(keys[t], m) : (unsigned)ej[q];
+      if (o + t < SNN_SHORT_CAP) sc[o + t] = v;
+    }
+  }
+  int P = 64;
+  while (P < n) P <<= 1;                                 // (n <= SNN_SHORT_CAP, a power of two)
+  for (int t = n + l; t < P; t += 64) sc[t] = 0xffffffffu;
+  __syncthreads();
+  static_assert(SNN_SHORT_CAP == 2048, "the sort's variants end at 2048 keys");
+  switch (P) {                                           // (the same branch in every lane)
+    case 64: snn_bitonic<0>(sc, l); break;
+    case 128: snn_bitonic<1>(sc, l); break;
+    case 256: snn_bitonic<2>(sc, l); break;
+    case 512: snn_bitonic<4>(sc, l); break;
+    case 1024: snn_bitonic<8>(sc, l); break;
+    default: snn_bitonic<16>(sc, l); break;
+  }
+  const long long ob = WRITE ? S.indptr[i] : 0, rowlen = WRITE ? S.indptr[i + 1] - ob : 0;
+  int base = 0;
+  for (int c = 0; c < n; c += 64) {
+    const int p = c + l;
+    bool keep = false;
+    unsigned key = 0;
+    int s = 0;
+    if (p < n) {
+      key = sc[p];
+      if (p == 0 || sc[p - 1] != key) {                  // the head of a run: its length is the shared count
+        int lo = p + 1, hi = n;
+        while (lo < hi) {
+          const int mid = (lo + hi) >> 1;
+          if (sc[mid] <= key) lo = mid + 1; else hi = mid;
+        }
+        s = lo - p;
+        keep = s >= S.s_min;
+      }
+    }
+    const u64 bal = __ballot(keep);
+    const long long pos = base + __popcll(bal & ((1ull << l) - 1));
+    if (WRITE && keep && pos < rowlen) { S.indices[ob + pos] = (int)key; S.weights[ob + pos] = S.jtab[min(s, m + 1)]; }
+    base += __popcll(bal);
+  }
+  if (!WRITE && l == 0) S.len[i] = (unsigned)base;
+}
+
+// one workgroup per long row: the index range in windows of SNN_WINDOW cells, an 8-bit counter per cell (s <= 129), swept in order
+template <bool WRITE>
+__global__ __launch_bounds__(256) void k_snn_long(SnnDev S) {
+  __shared__ unsigned cnt[SNN_WINDOW / 4];
+  __shared__ long long eb[SNN_MAX_K];
+  __shared__ int en[SNN_MAX_K], ej[SNN_MAX_K];
+  __shared__ int wtot[4];
+  __shared__ int any;
+  const int tid = threadIdx.x, l = tid & 63, wv = tid >> 6, m = S.m;
+  const unsigned nlong = (unsigned)min((long long)*S.nlong, S.N);
+  for (unsigned r = blockIdx.x; r < nlong; r += gridDim.x) {
+    const long long i = S.longrows[r];
+    for (int q = tid; q <= m; q += 256) {
+      const int j = snn_entry(S, i, q);
+      eb[q] = j >= 0 ? S.toff[j] : 0;
+      en[q] = j >= 0 ? (int)(S.toff[j + 1] - S.toff[j]) : 0;
+      ej[q] = j;
+    }
+    const long long ob = WRITE ? S.indptr[i] : 0, rowlen = WRITE ? S.indptr[i + 1] - ob : 0;
+    long long base = 0;
+    for (long long w0 = 0; w0 < S.N; w0 += SNN_WINDOW) {
+      const long long w1 = min(w0 + SNN_WINDOW, S.N);
+      for (int t = tid; t < SNN_WINDOW / 4; t += 256) cnt[t] = 0u;
+      if (tid == 0) any = 0;
+      __syncthreads();
+      for (int q = wv; q <= m; q += 4) {
+        const int j = ej[q];
+        if (j < 0) continue;
+        const u64* keys = S.tkey + eb[q];
+        const long long lo = lower_bound_keys(keys, en[q], (u64)w0 * (u64)m), hi = lower_bound_keys(keys, en[q], (u64)w1 * (u64)m);
+        for (long long t = lo + l; t < hi; t += 64) {
+          const unsigned off = (unsigned)((long long)snn_source(keys[t], m) - w0);
+          if (off < (unsigned)SNN_WINDOW) atomicAdd(&cnt[off >> 2], 1u << (8 * (off & 3)));
+        }
+        const bool own = j >= w0 && j < w1;
+        if (l == 0 && own) { const unsigned off = (unsigned)(j - w0); atomicAdd(&cnt[off >> 2], 1u << (8 * (off & 3))); }
+        if (l == 0 && (own || hi > lo)) atomicOr(&any, 1);
+      }
+      __syncthreads();
+      if (any) {                                         // (the same value in every thread: written before the barrier)
+        for (int c = 0; c < SNN_WINDOW; c += 1024) {
+          const unsigned word = cnt[(c >> 2) + tid];
+          const long long cell0 = w0 + c + 4 * tid;
+          int kept = 0;
+#pragma unroll
+          for (int b = 0; b < 4; b++) kept += ((int)((word >> (8 * b)) & 255u) >= S.s_min && cell0 + b < S.N) ? 1 : 0;
+          const int inc = wave_inclusive(kept, l);
+          if (l == 63) wtot[wv] = inc;
+          __syncthreads();
+          int before = 0, total = 0;
+#pragma unroll
+          for (int w = 0; w < 4; w++) { before += w < wv ? wtot[w] : 0; total += wtot[w]; }
+          if (WRITE) {
+            long long pos = base + before + inc - kept;
+#pragma unroll
+            for (int b = 0; b < 4; b++) {
+              const int s = (int)((word >> (8 * b)) & 255u);
+              if (s >= S.s_min && cell0 + b < S.N) {
+                if (pos < rowlen) { S.indices[ob + pos] = (int)(cell0 + b); S.weights[ob + pos] = S.jtab[min(s, m + 1)]; }
+                pos++;
+              }
+            }
+          }
+          base += total;
+          __syncthreads();
+        }
+      }
+      __syncthreads();
+    }
+    if (!WRITE && tid == 0) S.len[i] = (unsigned)base;
+    __syncthreads();
+  }
+}
+
 // ---- connected components ---------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_cc_check(CcDev C) {
   const int l = threadIdx.x & 63;
@@ -383,6 +600,16 @@ void l_graph_sort(const Launch& L, const GraphDev& G) {
 void l_graph_union(const Launch& L, const GraphDev& G, bool write) {
   if (write) hipLaunchKernelGGL(k_graph_union<true>, waves4(G.N), dim3(256), 0, L.stream, G);
   else hipLaunchKernelGGL(k_graph_union<false>, waves4(G.N), dim3(256), 0, L.stream, G);
+}
+void l_snn_indegree(const Launch& L, const GraphDev& G) { hipLaunchKernelGGL(k_snn_indegree, threads256(G.N * G.m), dim3(256), 0, L.stream, G); }
+void l_snn_rowweight(const Launch& L, const SnnDev& S) { hipLaunchKernelGGL(k_snn_rowweight, waves4(S.N), dim3(256), 0, L.stream, S); }
+void l_snn_short(const Launch& L, const SnnDev& S, bool write) {
+  if (write) hipLaunchKernelGGL(k_snn_short<true>, dim3((unsigned)S.N), dim3(64), 0, L.stream, S);
+  else hipLaunchKernelGGL(k_snn_short<false>, dim3((unsigned)S.N), dim3(64), 0, L.stream, S);
+}
+void l_snn_long(const Launch& L, const SnnDev& S, bool write) {
+  if (write) hipLaunchKernelGGL(k_snn_long<true>, dim3(SNN_LONG_WGS), dim3(256), 0, L.stream, S);
+  else hipLaunchKernelGGL(k_snn_long<false>, dim3(SNN_LONG_WGS), dim3(256), 0, L.stream, S);
 }
 void l_cc_check(const Launch& L, const CcDev& C) { hipLaunchKernelGGL(k_cc_check, waves4(C.N), dim3(256), 0, L.stream, C); }
 void l_cc_init(const Launch& L, const CcDev& C) { hipLaunchKernelGGL(k_cc_init, threads256(C.N), dim3(256), 0, L.stream, C); }

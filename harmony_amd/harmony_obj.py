@@ -324,6 +324,12 @@ class Harmony(object):
         from .graph import harmony_neighbors
         return harmony_neighbors(self, n_neighbors, prune_zeros)
 
+    def snn(self, k=20, prune=1.0 / 15.0):
+        """Seurat's shared-nearest-neighbour graph (snn.snn) of the handle's current Z_corr: (nn, snn) as scipy.sparse.csr_matrix, rows in the
+        order the cells were given in.  Z_corr is read where it lives in HBM; no host round trip."""
+        from .snn import harmony_snn
+        return harmony_snn(self, k, prune)
+
     def silhouette(self, meta_data, label_col, group_col=None, return_ab=False):
         """Silhouette widths (silhouette.silhouette_samples) of the handle's current Z_corr over the column `label_col` of meta_data, within the
         levels of `group_col` when one is named; one label per cell in the order the cells were given in.  Returns s, or (s, a, b).  Z_corr

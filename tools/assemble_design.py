@@ -231,6 +231,33 @@ if gr:
         missing.append("graph_kernel_stats.csv")
 else:
     vals["GRAPH_MEASURED"] = "**Not measured yet**: `profiles/graph_bench.json` (written by `tools/graph_bench.py` on an MI355X) is not in the tree."
+sn = line("snn_bench.json")      # tools/snn_bench.py
+if sn:
+    cpu = (" scipy's `A @ A.T` with the same pruning on that machine's CPU (one thread): %.1f s, %.0f times the SNN stage; its result equals the library's: %s."
+           % (sn["cpu_scipy_ms"] / 1e3, sn["cpu_scipy_ms"] / sn["snn_ms"], "yes" if sn["equals_scipy"] else "NO")) if "cpu_scipy_ms" in sn else ""
+    vals["SNN_MEASURED"] = ("**Measured** (`profiles/snn_bench.json`, one MI355X, %s cells x %d PCs, float32 on the host, k = %d, prune = %.4f so s_min = %d, medians by the "
+                            "library's timers): kNN %.0f ms, SNN stage %.1f ms (spread %.1f %% over %d calls) = %.1f %% of the kNN in front of it, CSR copy of %.0f MB "
+                            "included; %s entries = %.1f per row = %.2f N k against the first capacity of 6 N k (retried: %s); Σ C_i = %s candidates (%.0f per row, at most %d), "
+                            "%d rows on the long path, largest in-degree %d; the same bits in every call: %s.%s"
+                            % ("{:,}".format(sn["cells"]).replace(",", " "), sn["d"], sn["k"], sn["prune"], sn["s_min"], sn["knn_ms"], sn["snn_ms"], 100.0 * sn["snn_spread"],
+                               len(sn["snn_ms_all"]), 100.0 * sn["snn_share_of_knn"], sn["csr_copy_bytes"] / 1e6, "{:,}".format(sn["entries"]).replace(",", " "),
+                               sn["entries_per_row"], sn["entries"] / (float(sn["cells"]) * sn["k"]), "yes" if sn["retried"] else "no",
+                               "{:,}".format(sn["sum_candidates"]).replace(",", " "), sn["sum_candidates"] / float(sn["cells"]), sn["max_candidates"], sn["long_rows"],
+                               sn["max_in_degree"], "yes" if sn["same_bits_every_call"] else "NO", cpu))
+    try:      # the kernel table of two calls (rocprofv3 --kernel-trace --stats, a run of its own)
+        import csv
+        ks = []
+        for row in csv.DictReader(open(os.path.join(P, "snn_kernel_stats.csv"))):
+            name = row["Name"].replace("void ", "").replace("hmx::", "").split("(")[0]
+            if name.startswith(("k_snn_", "k_graph_", "k_scan_", "k_knn")):
+                ks.append((float(row["AverageNs"]) / 1e6, int(row["Calls"]), name))
+        vals["SNN_KERNELS"] = "; ".join("`%s` %.3f ms x %d" % (n, ms, c) for ms, c, n in sorted(ks, reverse=True))
+    except Exception:
+        vals["SNN_KERNELS"] = "not traced yet (`profiles/snn_kernel_stats.csv` is not in the tree)"
+        missing.append("snn_kernel_stats.csv")
+else:
+    vals["SNN_MEASURED"] = "**Not measured yet**: `profiles/snn_bench.json` (written by `tools/snn_bench.py` on an MI355X) is not in the tree."
+    vals["SNN_KERNELS"] = "not traced yet"
 parts = sorted(f for f in os.listdir(os.path.join(ROOT, "docs", "design_parts")) if f.endswith(".md"))
 out = io.StringIO()
 for f in parts:

@@ -4,7 +4,13 @@ handle's own state, so nothing drifts and the bars sit near fp32 rounding.  Ever
 The o_ .. r_ cases walk the branches of the launch plan (harmony_amd/csrc/hmx_plan.h) on the block count -- 63 | 64 | 65 | 100 | 1000 blocks --, the
 d window 65..76 and the launch geometry switches; tests/test_stage_ref_cpu.py holds their claimed paths to the plan itself, without a GPU.
 The round ladder (run_ladder) judges what a round hands to the next one -- carried old contributions, elided R stores, the 4-round sort
-groups -- against the same spec."""
+groups -- against the same spec.
+The t01_ .. t16_ cases (LATTICE) are small shapes, one per kernel instantiation the others leave out; tests/stage_lattice.py proves on the CPU that all cases together
+launch every instantiation the plan reaches at such shapes, and each lattice case asserts that the instantiation that ran is the one it is credited with.  What a case
+would catch: in k_tile<3, 0, 2, false> of the split-bf16 build (the update, per-cluster sigma) only t03_K40_d80_v runs, with K = 40 on 48 columns: by kcol (hmx_internal.h)
+lane c holds clusters 3 c + {0, 1, 2}, so lane 13 holds 39 | 40 | 41 -- one valid, two past K -- and lanes 14 and 15 none.  Two cluster columns exchanged at that edge
+(38 and 39, say) leave round_R off by |R[38] - R[39]| of the cells near either cluster (bar 1e-5) and its O / E tables by whole columns (bar 3e-7).
+No other case launches that instantiation."""
 import json
 import os
 import sys
@@ -17,16 +23,21 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-from harmony_amd import Harmony, harmony_options, prepare_setup_args  # noqa: E402
+from harmony_amd import Harmony, HarmonyError, harmony_options, prepare_setup_args  # noqa: E402
 from helpers import synth  # noqa: E402
 from oracle.oracle import feistel_order  # noqa: E402
 from stage_check import run_ladder, run_stages  # noqa: E402
+from test_plan_cpu import LAUNCH_FIELDS, RIDGE_FIELDS  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 # Bars: at most 10x the worst error measured over these cases on an MI355X (in brackets).  Both sides share the fp32 inputs; what is left is
 # the library's own fp32 rounding.  The o_ .. r_ cases and the round ladders stay below the a_ .. n_ figures in every column (d = 68 / 76: R 3.7e-6 /
 # 3.9e-6 under R_d128; the ladders' rungs: R 2.0e-6 .. 2.3e-6, tables 2.8e-8, objective 1.2e-7 .. 2.7e-7): no bar was added or moved for them.
+# The LATTICE cases (73 small shapes, one per kernel instantiation the older cases leave out) use the same bars.  Worst figures on an MI355X (over the 72 cases of the set cover; t16_K232_d64_v, added by hand, passes the same bars): R 2.3e-6 (d <= 64,
+# t08_K128_d64_u) and 4.4e-6 (d > 64, t03_K33_d128_v_dotf32), O 8.6e-8 / E 8.1e-8 and stale objective 1.4e-7 (all three at t16_K225_d1_u: d = 1, every cell is +1 or -1),
+# objective 3.5e-7, Z_corr 1.1e-7 rel. / 2.7e-7 max-abs, Y 6.1e-9, W 1.2e-8, Lambda 7.2e-8, no argmax off; the two-round ladders of the chain without R stores: R 1.8e-6,
+# tables 2.8e-8, objective 2.8e-7.  The tables and the stale objective exceed the older cases' worst (3.0e-8, 3.7e-8) and stay below a third of their bars.
 BARS = {
     "R": 5e-6,          # teacher-forced R, max-abs, d <= 64 [2.7e-6]
     "R_d128": 1e-5,     # ... d = 128: dist sums more than twice as many fp32 products, and R moves by R (1 - R) ddist / sigma [5.1e-6]
@@ -65,6 +76,11 @@ def _case(name, cus=256):
     if name.endswith("_pushed") and name[:-7] in PUSHED:      # the same case under host-injected orders (prepare_round's pos / cells_per_block path)
         Z, meta, var, kw, env, seed, path = _case(name[:-7], cus)
         return Z, meta, var, kw, env, seed, dict(path, push=1)
+    if name in LATTICE:
+        N, d, levels, K, sigma, env, dseed, path, _credit = LATTICE[name]
+        Z, meta, _ = synth(N, d=d, levels=levels, seed=dseed)
+        kw = dict(nclust=K) if sigma == "u" else dict(nclust=K, sigma=0.08 + 0.07 * np.random.default_rng(dseed).random(K))
+        return Z, meta, sorted(meta), kw, env, dseed, path
     if name == "a_chain_schur":
         Z, meta, _ = synth(100000, d=50, levels=(10,), seed=1)
         return Z, meta, "cov0", dict(nclust=100), o, 3, dict(chain=1, chain_pair=0, usig=1, upd_wps=2, host=0, min_kept=8)
@@ -162,6 +178,235 @@ PLAN_CASES = ["o_blocks_100", "o_blocks_63_carried", "o_blocks_64", "o_blocks_65
               "q_d68_fp32_on_the_chain", "q_d76_fp32_on_the_chain", "r_launch_geometry"]
 PUSHED = ["o_blocks_100", "o_blocks_65", "o_blocks_1000_four_waves"]
 CASES += PLAN_CASES + [n + "_pushed" for n in PUSHED]
+# ---- one small case per kernel instantiation: chosen by greedy set cover over the coverage ledger (tests/stage_lattice.py, tools/make_stage_lattice.py) so that, with the
+#      cases above and the ladders, every k_tile head / update / chain / wave-pair variant of both builds and every ridge statistics / apply kernel that the plan reaches at
+#      4000 - 6000 cells is launched by a case.  K: per cluster-tile count a full last tile (16 NCT), one valid lane in it (16 (NCT - 1) + 1), inside a quad (16 NCT - 8 | 4) and
+#      the lowest K of a kernel that serves two tile counts (129, 225); d rotated over 1 .. 128 (68 / 72 / 76: the fp32 build without a switch; 64 with K = 128: statistics
+#      without LDS shadows); u | v: uniform | per-cluster sigma; c2: two covariates.
+#      name -> (cells, PCs, levels, clusters, sigma form, environment, seed of the data and the handle, the path it claims, the launches the ledger credits it with:
+#      k_tile (bf, nct, mode, wps, usig), ridge (mfma, p0, p1)); tests/test_stage_ref_cpu.py holds both to the plan for the case's own design
+LATTICE = {
+    't01_K8_d32_v': (4000, 32, (4,), 8, 'v', {}, 200,
+        {'chain': 1, 'chain_pair': 0, 'usig': 0, 'upd_wps': 2, 'dot_bf': 1, 'moe_mfma': 1, 'host': 0},
+        {'head': (1, 1, 1, 2, 0), 'chain': (1, 1, 4, 2, 0), 'stats': (1, 1, 1), 'apply': (1, 2, 0)}),
+    't01_K8_d100_u_dotf32': (4000, 100, (4,), 8, 'u', {'HMX_DOT': 'f32'}, 201,
+        {'chain': 0, 'chain_pair': 0, 'usig': 1, 'upd_wps': 4, 'dot_bf': 0, 'moe_mfma': 0, 'host': 0},
+        {'head': (0, 1, 1, 4, 1), 'update': (0, 1, 0, 4, 1), 'stats': (0, 28, 0), 'apply': (0, 1, 2)}),
+    't01_K8_d128_v': (4000, 128, (4,), 8, 'v', {}, 202,
+        {'chain': 0, 'chain_pair': 0, 'usig': 0, 'upd_wps': 2, 'dot_bf': 1, 'moe_mfma': 0, 'host': 0},
+        {'head': (1, 1, 1, 2, 0), 'update': (1, 1, 0, 2, 0), 'stats': (0, 32, 0), 'apply': (0, 1, 2)}),
+    't01_K16_d8_u_dotf32': (4000, 8, (4,), 16, 'u', {'HMX_DOT': 'f32'}, 203,
+        {'chain': 1, 'chain_pair': 0, 'usig': 1, 'upd_wps': 4, 'dot_bf': 0, 'moe_mfma': 1, 'host': 0},
+        {'head': (0, 1, 1, 4, 1), 'chain': (0, 1, 4, 2, 1), 'stats': (1, 1, 1), 'apply': (1, 1, 0)}),
+    't01_K16_d76_v': (4000, 76, (4,), 16, 'v', {}, 204,
+        {'chain': 1, 'chain_pair': 0, 'usig': 0, 'upd_wps': 2, 'dot_bf': 0, 'moe_mfma': 0, 'host': 0},
+        {'head': (0, 1, 1, 2, 0), 'chain': (0, 1, 4, 2, 0), 'stats': (0, 28, 0), 'apply': (0, 1, 2)}),
+    't01_K16_d76_v_c2_chain0': (4000, 76, (3, 2), 16, 'v', {'HMX_CHAIN': '0'}, 205,
+        {'chain': 0, 'chain_pair': 0, 'usig': 0, 'upd_wps': 2, 'dot_bf': 0, 'moe_mfma': 0, 'host': 0},
+        {'head': (0, 1, 1, 2, 0), 'update': (0, 1, 0, 2, 0), 'stats': (0, 28, 0), 'apply': (0, 1, 2)}),
+    't01_K16_d80_u_c2': (4000, 80, (3, 2), 16, 'u', {}, 206,
+        {'chain': 0, 'chain_pair': 0, 'usig': 1, 'upd_wps': 4, 'dot_bf': 1, 'moe_mfma': 0, 'host': 0},
+        {'head': (1, 1, 1, 4, 1), 'update': (1, 1, 0, 4, 1), 'stats': (0, 28, 0), 'apply': (0, 1, 2)}),
+    't02_K17_d96_v_c2': (4000, 96, (3, 2), 17, 'v', {}, 207,
+        {'chain': 0, 'chain_pair': 0, 'usig': 0, 'upd_wps': 2, 'dot_bf': 1, 'moe_mfma': 0, 'host': 0},
+        {'head': (1, 2, 1, 2, 0), 'update': (1, 2, 0, 2, 0), 'stats': (0, 32, 0), 'apply': (0, 1, 2)}),
+    't02_K17_d128_u': (4000, 128, (4,), 17, 'u', {}, 208,
+        {'chain': 0, 'chain_pair': 0, 'usig': 1, 'upd_wps': 4, 'dot_bf': 1, 'moe_mfma': 0, 'host': 0},
+        {'head': (1, 2, 1, 4, 1), 'update': (1, 2, 0, 4, 1), 'stats': (0, 32, 0), 'apply': (0, 1, 2)}),
+    't02_K24_d65_u_c2': (4000, 65, (3, 2), 24, 'u', {}, 209,
+        {'chain': 1, 'chain_pair': 0, 'usig': 1, 'upd_wps': 4, 'dot_bf': 0, 'moe_mfma': 0, 'host': 0},
+        {'head': (0, 2, 1, 4, 1), 'chain': (0, 2, 4, 2, 1), 'stats': (0, 24, 0), 'apply': (0, 1, 2)}),
+    't02_K24_d68_v': (4000, 68, (4,), 24, 'v', {}, 210,
+        {'chain': 1, 'chain_pair': 0, 'usig': 0, 'upd_wps': 2, 'dot_bf': 0, 'moe_mfma': 0, 'host': 0},
+        {'head': (0, 2, 1, 2, 0), 'chain': (0, 2, 4, 2, 0), 'stats': (0, 24, 0), 'apply': (0, 1, 2)}),
+    't02_K32_d17_v_c2': (4000, 17, (3, 2), 32, 'v', {}, 211,
+        {'chain': 1, 'chain_pair': 0, 'usig': 0, 'upd_wps': 2, 'dot_bf': 1, 'moe_mfma': 1, 'host': 0},
+        {'head': (1, 2, 1, 2, 0), 'chain': (1, 2, 4, 2, 0), 'stats': (1, 2, 1), 'apply': (1, 2, 0)}),
+    't02_K32_d80_u_dotf32': (4000, 80, (4,), 32, 'u', {'HMX_DOT': 'f32'}, 212,
+        {'chain': 0, 'chain_pair': 0, 'usig': 1, 'upd_wps': 4, 'dot_bf': 0, 'moe_mfma': 0, 'host': 0},
+        {'head': (0, 2, 1, 4, 1), 'update': (0, 2, 0, 4, 1), 'stats': (0, 28, 0), 'apply': (0, 1, 2)}),
+    't02_K32_d128_v_c2_dotf32': (4000, 128, (3, 2), 32, 'v', {'HMX_DOT': 'f32'}, 213,
+        {'chain': 0, 'chain_pair': 0, 'usig': 0, 'upd_wps': 2, 'dot_bf': 0, 'moe_mfma': 0, 'host': 0},
+        {'head': (0, 2, 1, 2, 0), 'update': (0, 2, 0, 2, 0), 'stats': (0, 32, 0), 'apply': (0, 1, 2)}),
+    't03_K33_d76_v_c2': (4000, 76, (3, 2), 33, 'v', {}, 214,
+        {'chain': 1, 'chain_pair': 0, 'usig': 0, 'upd_wps': 2, 'dot_bf': 0, 'moe_mfma': 0, 'host': 0},
+        {'head': (0, 3, 1, 2, 0), 'chain': (0, 3, 4, 2, 0), 'stats': (0, 28, 0), 'apply': (0, 1, 2)}),
+    't03_K33_d128_v_dotf32': (4000, 128, (4,), 33, 'v', {'HMX_DOT': 'f32'}, 215,
+        {'chain': 0, 'chain_pair': 0, 'usig': 0, 'upd_wps': 2, 'dot_bf': 0, 'moe_mfma': 0, 'host': 0},
+        {'head': (0, 3, 1, 2, 0), 'update': (0, 3, 0, 2, 0), 'stats': (0, 32, 0), 'apply': (0, 1, 2)}),
+    't03_K40_d80_v': (4000, 80, (4,), 40, 'v', {}, 216,
+        {'chain': 0, 'chain_pair': 0, 'usig': 0, 'upd_wps': 2, 'dot_bf': 1, 'moe_mfma': 0, 'host': 0},
+        {'head': (1, 3, 1, 2, 0), 'update': (1, 3, 0, 2, 0), 'stats': (0, 28, 0), 'apply': (0, 1, 2)}),
+    't03_K48_d68_u': (4000, 68, (4,), 48, 'u', {}, 217,
+        {'chain': 1, 'chain_pair': 0, 'usig': 1, 'upd_wps': 4, 'dot_bf': 0, 'moe_mfma': 0, 'host': 0},
+        {'head': (0, 3, 1, 4, 1), 'chain': (0, 3, 4, 2, 1), 'stats': (0, 24, 0), 'apply': (0, 1, 2)}),
+    't03_K48_d100_u_c2_dotf32': (4000, 100, (3, 2), 48, 'u', {'HMX_DOT': 'f32'}, 218,
+        {'chain': 0, 'chain_pair': 0, 'usig': 1, 'upd_wps': 4, 'dot_bf': 0, 'moe_mfma': 0, 'host': 0},
+        {'head': (0, 3, 1, 4, 1), 'update': (0, 3, 0, 4, 1), 'stats': (0, 28, 0), 'apply': (0, 1, 2)}),
+    't04_K49_d80_v': (4000, 80, (4,), 49, 'v', {}, 219,
+        {'chain': 0, 'chain_pair': 0, 'usig': 0, 'upd_wps': 2, 'dot_bf': 1, 'moe_mfma': 0, 'host': 0},
+        {'head': (1, 4, 1, 2, 0), 'update': (1, 4, 0, 2, 0), 'stats': (0, 28, 0), 'apply': (0, 1, 2)}),
+    't04_K49_d96_u_c2': (4000, 96, (3, 2), 49, 'u', {}, 220,
+        {'chain': 0, 'chain_pair': 0, 'usig': 1, 'upd_wps': 4, 'dot_bf': 1, 'moe_mfma': 0, 'host': 0},
+        {'head': (1, 4, 1, 4, 1), 'update': (1, 4, 0, 4, 1), 'stats': (0, 32, 0), 'apply': (0, 1, 2)}),
+    't04_K56_d72_v': (4000, 72, (4,), 56, 'v', {}, 221,
+        {'chain': 1, 'chain_pair': 0, 'usig': 0, 'upd_wps': 2, 'dot_bf': 0, 'moe_mfma': 0, 'host': 0},
+        {'head': (0, 4, 1, 2, 0), 'chain': (0, 4, 4, 2, 0), 'stats': (0, 24, 0), 'apply': (0, 1, 2)}),
+    't04_K56_d76_u_c2': (4000, 76, (3, 2), 56, 'u', {}, 222,
+        {'chain': 1, 'chain_pair': 0, 'usig': 1, 'upd_wps': 4, 'dot_bf': 0, 'moe_mfma': 0, 'host': 0},
+        {'head': (0, 4, 1, 4, 1), 'chain': (0, 4, 4, 2, 1), 'stats': (0, 28, 0), 'apply': (0, 1, 2)}),
+    't04_K64_d48_v': (4000, 48, (4,), 64, 'v', {}, 223,
+        {'chain': 1, 'chain_pair': 0, 'usig': 0, 'upd_wps': 2, 'dot_bf': 1, 'moe_mfma': 1, 'host': 0},
+        {'head': (1, 4, 1, 2, 0), 'chain': (1, 4, 4, 2, 0), 'stats': (1, 4, 1), 'apply': (1, 3, 0)}),
+    't04_K64_d96_v_dotf32': (4000, 96, (4,), 64, 'v', {'HMX_DOT': 'f32'}, 224,
+        {'chain': 0, 'chain_pair': 0, 'usig': 0, 'upd_wps': 2, 'dot_bf': 0, 'moe_mfma': 0, 'host': 0},
+        {'head': (0, 4, 1, 2, 0), 'update': (0, 4, 0, 2, 0), 'stats': (0, 32, 0), 'apply': (0, 1, 2)}),
+    't04_K64_d116_u_dotf32': (4000, 116, (4,), 64, 'u', {'HMX_DOT': 'f32'}, 225,
+        {'chain': 0, 'chain_pair': 0, 'usig': 1, 'upd_wps': 4, 'dot_bf': 0, 'moe_mfma': 0, 'host': 0},
+        {'head': (0, 4, 1, 4, 1), 'update': (0, 4, 0, 4, 1), 'stats': (0, 32, 0), 'apply': (0, 1, 2)}),
+    't05_K65_d116_v_c2': (4000, 116, (3, 2), 65, 'v', {}, 226,
+        {'chain': 0, 'chain_pair': 0, 'usig': 0, 'upd_wps': 2, 'dot_bf': 1, 'moe_mfma': 0, 'host': 0},
+        {'head': (1, 5, 1, 2, 0), 'update': (1, 5, 0, 2, 0), 'stats': (0, 32, 0), 'apply': (0, 2, 2)}),
+    't05_K65_d116_u': (4000, 116, (4,), 65, 'u', {}, 227,
+        {'chain': 0, 'chain_pair': 0, 'usig': 1, 'upd_wps': 2, 'dot_bf': 1, 'moe_mfma': 0, 'host': 0},
+        {'head': (1, 5, 1, 2, 1), 'update': (1, 5, 0, 2, 1), 'stats': (0, 32, 0), 'apply': (0, 2, 2)}),
+    't05_K72_d65_v_c2': (4000, 65, (3, 2), 72, 'v', {}, 228,
+        {'chain': 1, 'chain_pair': 0, 'usig': 0, 'upd_wps': 2, 'dot_bf': 0, 'moe_mfma': 0, 'host': 0},
+        {'head': (0, 5, 1, 2, 0), 'chain': (0, 5, 4, 2, 0), 'stats': (0, 24, 0), 'apply': (0, 2, 2)}),
+    't05_K72_d96_u_c2_dotf32': (4000, 96, (3, 2), 72, 'u', {'HMX_DOT': 'f32'}, 229,
+        {'chain': 0, 'chain_pair': 0, 'usig': 1, 'upd_wps': 2, 'dot_bf': 0, 'moe_mfma': 0, 'host': 0},
+        {'head': (0, 5, 1, 2, 1), 'update': (0, 5, 0, 2, 1), 'stats': (0, 32, 0), 'apply': (0, 2, 2)}),
+    't05_K80_d63_v_c2': (4000, 63, (3, 2), 80, 'v', {}, 230,
+        {'chain': 1, 'chain_pair': 0, 'usig': 0, 'upd_wps': 2, 'dot_bf': 1, 'moe_mfma': 1, 'host': 0},
+        {'head': (1, 5, 1, 2, 0), 'chain': (1, 5, 4, 2, 0), 'stats': (1, 5, 1), 'apply': (1, 4, 0)}),
+    't05_K80_d76_u_c2': (4000, 76, (3, 2), 80, 'u', {}, 231,
+        {'chain': 1, 'chain_pair': 0, 'usig': 1, 'upd_wps': 2, 'dot_bf': 0, 'moe_mfma': 0, 'host': 0},
+        {'head': (0, 5, 1, 2, 1), 'chain': (0, 5, 4, 2, 1), 'stats': (0, 28, 0), 'apply': (0, 2, 2)}),
+    't05_K80_d116_v_c2_dotf32': (4000, 116, (3, 2), 80, 'v', {'HMX_DOT': 'f32'}, 232,
+        {'chain': 0, 'chain_pair': 0, 'usig': 0, 'upd_wps': 2, 'dot_bf': 0, 'moe_mfma': 0, 'host': 0},
+        {'head': (0, 5, 1, 2, 0), 'update': (0, 5, 0, 2, 0), 'stats': (0, 32, 0), 'apply': (0, 2, 2)}),
+    't06_K81_d17_v': (4000, 17, (4,), 81, 'v', {}, 233,
+        {'chain': 1, 'chain_pair': 0, 'usig': 0, 'upd_wps': 2, 'dot_bf': 1, 'moe_mfma': 0, 'host': 0},
+        {'head': (1, 6, 1, 2, 0), 'chain': (1, 6, 4, 2, 0), 'stats': (0, 20, 0), 'apply': (0, 2, 1)}),
+    't06_K81_d100_v_c2': (4000, 100, (3, 2), 81, 'v', {}, 234,
+        {'chain': 0, 'chain_pair': 0, 'usig': 0, 'upd_wps': 2, 'dot_bf': 1, 'moe_mfma': 0, 'host': 0},
+        {'head': (1, 6, 1, 2, 0), 'update': (1, 6, 0, 2, 0), 'stats': (0, 28, 0), 'apply': (0, 2, 2)}),
+    't06_K88_d68_v': (4000, 68, (4,), 88, 'v', {}, 235,
+        {'chain': 1, 'chain_pair': 0, 'usig': 0, 'upd_wps': 2, 'dot_bf': 0, 'moe_mfma': 0, 'host': 0},
+        {'head': (0, 6, 1, 2, 0), 'chain': (0, 6, 4, 2, 0), 'stats': (0, 24, 0), 'apply': (0, 2, 2)}),
+    't06_K88_d116_u_dotf32': (4000, 116, (4,), 88, 'u', {'HMX_DOT': 'f32'}, 236,
+        {'chain': 0, 'chain_pair': 0, 'usig': 1, 'upd_wps': 2, 'dot_bf': 0, 'moe_mfma': 0, 'host': 0},
+        {'head': (0, 6, 1, 2, 1), 'update': (0, 6, 0, 2, 1), 'stats': (0, 32, 0), 'apply': (0, 2, 2)}),
+    't06_K96_d32_u_c2_dotf32': (4000, 32, (3, 2), 96, 'u', {'HMX_DOT': 'f32'}, 237,
+        {'chain': 1, 'chain_pair': 0, 'usig': 1, 'upd_wps': 2, 'dot_bf': 0, 'moe_mfma': 1, 'host': 0},
+        {'head': (0, 6, 1, 2, 1), 'chain': (0, 6, 4, 2, 1), 'stats': (1, 6, 1), 'apply': (1, 2, 0)}),
+    't06_K96_d68_v_chain0': (4000, 68, (4,), 96, 'v', {'HMX_CHAIN': '0'}, 238,
+        {'chain': 0, 'chain_pair': 0, 'usig': 0, 'upd_wps': 2, 'dot_bf': 0, 'moe_mfma': 0, 'host': 0},
+        {'head': (0, 6, 1, 2, 0), 'update': (0, 6, 0, 2, 0), 'stats': (0, 24, 0), 'apply': (0, 2, 2)}),
+    't06_K96_d80_u': (4000, 80, (4,), 96, 'u', {}, 239,
+        {'chain': 0, 'chain_pair': 0, 'usig': 1, 'upd_wps': 2, 'dot_bf': 1, 'moe_mfma': 0, 'host': 0},
+        {'head': (1, 6, 1, 2, 1), 'update': (1, 6, 0, 2, 1), 'stats': (0, 28, 0), 'apply': (0, 2, 2)}),
+    't07_K97_d65_v_chain0': (4000, 65, (4,), 97, 'v', {'HMX_CHAIN': '0'}, 240,
+        {'chain': 0, 'chain_pair': 0, 'usig': 0, 'upd_wps': 2, 'dot_bf': 0, 'moe_mfma': 0, 'host': 0},
+        {'head': (0, 7, 1, 2, 0), 'update': (0, 7, 0, 2, 0), 'stats': (0, 24, 0), 'apply': (0, 2, 2)}),
+    't07_K97_d76_v_c2': (4000, 76, (3, 2), 97, 'v', {}, 241,
+        {'chain': 1, 'chain_pair': 0, 'usig': 0, 'upd_wps': 2, 'dot_bf': 0, 'moe_mfma': 0, 'host': 0},
+        {'head': (0, 7, 1, 2, 0), 'chain': (0, 7, 4, 2, 0), 'stats': (0, 28, 0), 'apply': (0, 2, 2)}),
+    't07_K104_d100_v_c2': (4000, 100, (3, 2), 104, 'v', {}, 242,
+        {'chain': 0, 'chain_pair': 0, 'usig': 0, 'upd_wps': 2, 'dot_bf': 1, 'moe_mfma': 0, 'host': 0},
+        {'head': (1, 7, 1, 2, 0), 'update': (1, 7, 0, 2, 0), 'stats': (0, 28, 0), 'apply': (0, 2, 2)}),
+    't07_K112_d63_v_c2': (4000, 63, (3, 2), 112, 'v', {}, 243,
+        {'chain': 1, 'chain_pair': 0, 'usig': 0, 'upd_wps': 2, 'dot_bf': 1, 'moe_mfma': 1, 'host': 0},
+        {'head': (1, 7, 1, 2, 0), 'chain': (1, 7, 4, 2, 0), 'stats': (1, 7, 1), 'apply': (1, 4, 0)}),
+    't07_K112_d72_u_c2_chain0': (4000, 72, (3, 2), 112, 'u', {'HMX_CHAIN': '0'}, 244,
+        {'chain': 0, 'chain_pair': 0, 'usig': 1, 'upd_wps': 2, 'dot_bf': 0, 'moe_mfma': 0, 'host': 0},
+        {'head': (0, 7, 1, 2, 1), 'update': (0, 7, 0, 2, 1), 'stats': (0, 24, 0), 'apply': (0, 2, 2)}),
+    't08_K113_d16_u': (4000, 16, (4,), 113, 'u', {}, 245,
+        {'chain': 0, 'chain_pair': 0, 'usig': 1, 'upd_wps': 2, 'dot_bf': 1, 'moe_mfma': 0, 'host': 0},
+        {'head': (1, 8, 1, 2, 1), 'update': (1, 8, 0, 2, 1), 'stats': (0, 16, 0), 'apply': (0, 2, 1)}),
+    't08_K113_d72_u': (4000, 72, (4,), 113, 'u', {}, 246,
+        {'chain': 0, 'chain_pair': 0, 'usig': 1, 'upd_wps': 2, 'dot_bf': 0, 'moe_mfma': 0, 'host': 0},
+        {'head': (0, 8, 1, 2, 1), 'update': (0, 8, 0, 2, 1), 'stats': (0, 24, 0), 'apply': (0, 2, 2)}),
+    't08_K120_d60_v': (4000, 60, (4,), 120, 'v', {}, 247,
+        {'chain': 0, 'chain_pair': 0, 'usig': 0, 'upd_wps': 2, 'dot_bf': 1, 'moe_mfma': 1, 'host': 0},
+        {'head': (1, 8, 1, 2, 0), 'update': (1, 8, 0, 2, 0), 'stats': (1, 8, 1), 'apply': (1, 4, 0)}),
+    't08_K128_d64_u': (4000, 64, (4,), 128, 'u', {}, 248,
+        {'chain': 1, 'chain_pair': 1, 'usig': 1, 'upd_wps': 2, 'dot_bf': 1, 'moe_mfma': 1, 'host': 0},
+        {'head': (1, 8, 1, 2, 1), 'chain': (1, 4, 6, 2, 1), 'stats': (1, 8, 0), 'apply': (1, 4, 0)}),
+    't08_K128_d72_v_c2': (4000, 72, (3, 2), 128, 'v', {}, 249,
+        {'chain': 0, 'chain_pair': 0, 'usig': 0, 'upd_wps': 2, 'dot_bf': 0, 'moe_mfma': 0, 'host': 0},
+        {'head': (0, 8, 1, 2, 0), 'update': (0, 8, 0, 2, 0), 'stats': (0, 24, 0), 'apply': (0, 2, 2)}),
+    't10_K129_d3_u': (4000, 3, (4,), 129, 'u', {}, 250,
+        {'chain': 0, 'chain_pair': 0, 'usig': 1, 'upd_wps': 2, 'dot_bf': 1, 'moe_mfma': 0, 'host': 0},
+        {'head': (1, 10, 1, 2, 1), 'update': (1, 10, 0, 2, 1), 'stats': (0, 4, 0), 'apply': (0, 3, 1)}),
+    't10_K145_d1_v_c2': (4000, 1, (3, 2), 145, 'v', {}, 251,
+        {'chain': 0, 'chain_pair': 0, 'usig': 0, 'upd_wps': 2, 'dot_bf': 1, 'moe_mfma': 0, 'host': 0},
+        {'head': (1, 10, 1, 2, 0), 'update': (1, 10, 0, 2, 0), 'stats': (0, 4, 0), 'apply': (0, 3, 1)}),
+    't10_K152_d72_v': (4000, 72, (4,), 152, 'v', {}, 252,
+        {'chain': 0, 'chain_pair': 0, 'usig': 0, 'upd_wps': 2, 'dot_bf': 0, 'moe_mfma': 0, 'host': 0},
+        {'head': (0, 10, 1, 2, 0), 'update': (0, 10, 0, 2, 0), 'stats': (0, 24, 0), 'apply': (0, 3, 2)}),
+    't10_K160_d60_u_c2': (4000, 60, (3, 2), 160, 'u', {}, 253,
+        {'chain': 1, 'chain_pair': 1, 'usig': 1, 'upd_wps': 2, 'dot_bf': 1, 'moe_mfma': 1, 'host': 0},
+        {'head': (1, 10, 1, 2, 1), 'chain': (1, 5, 6, 2, 1), 'stats': (1, 5, 1), 'apply': (1, 4, 0)}),
+    't10_K160_d68_u_c2': (4000, 68, (3, 2), 160, 'u', {}, 254,
+        {'chain': 0, 'chain_pair': 0, 'usig': 1, 'upd_wps': 2, 'dot_bf': 0, 'moe_mfma': 0, 'host': 0},
+        {'head': (0, 10, 1, 2, 1), 'update': (0, 10, 0, 2, 1), 'stats': (0, 24, 0), 'apply': (0, 3, 2)}),
+    't12_K161_d65_v_c2': (4000, 65, (3, 2), 161, 'v', {}, 255,
+        {'chain': 0, 'chain_pair': 0, 'usig': 0, 'upd_wps': 2, 'dot_bf': 0, 'moe_mfma': 0, 'host': 0},
+        {'head': (0, 12, 1, 2, 0), 'update': (0, 12, 0, 2, 0), 'stats': (0, 24, 0), 'apply': (0, 3, 2)}),
+    't12_K177_d3_u': (4000, 3, (4,), 177, 'u', {}, 256,
+        {'chain': 0, 'chain_pair': 0, 'usig': 1, 'upd_wps': 2, 'dot_bf': 1, 'moe_mfma': 0, 'host': 0},
+        {'head': (1, 12, 1, 2, 1), 'update': (1, 12, 0, 2, 1), 'stats': (0, 4, 0), 'apply': (0, 3, 1)}),
+    't12_K184_d50_v': (4000, 50, (4,), 184, 'v', {}, 257,
+        {'chain': 0, 'chain_pair': 0, 'usig': 0, 'upd_wps': 2, 'dot_bf': 1, 'moe_mfma': 1, 'host': 0},
+        {'head': (1, 12, 1, 2, 0), 'update': (1, 12, 0, 2, 0), 'stats': (1, 6, 1), 'apply': (1, 4, 0)}),
+    't12_K192_d24_u': (4000, 24, (4,), 192, 'u', {}, 258,
+        {'chain': 1, 'chain_pair': 1, 'usig': 1, 'upd_wps': 2, 'dot_bf': 1, 'moe_mfma': 1, 'host': 0},
+        {'head': (1, 12, 1, 2, 1), 'chain': (1, 6, 6, 2, 1), 'stats': (1, 6, 1), 'apply': (1, 2, 0)}),
+    't12_K192_d65_u_c2': (4000, 65, (3, 2), 192, 'u', {}, 259,
+        {'chain': 0, 'chain_pair': 0, 'usig': 1, 'upd_wps': 2, 'dot_bf': 0, 'moe_mfma': 0, 'host': 0},
+        {'head': (0, 12, 1, 2, 1), 'update': (0, 12, 0, 2, 1), 'stats': (0, 24, 0), 'apply': (0, 3, 2)}),
+    't13_K193_d8_u_c2': (4000, 8, (3, 2), 193, 'u', {}, 260,
+        {'chain': 0, 'chain_pair': 0, 'usig': 1, 'upd_wps': 2, 'dot_bf': 1, 'moe_mfma': 0, 'host': 0},
+        {'head': (1, 13, 1, 2, 1), 'update': (1, 13, 0, 2, 1), 'stats': (0, 8, 0), 'apply': (0, 4, 1)}),
+    't13_K193_d16_u_c2_dotf32': (4000, 16, (3, 2), 193, 'u', {'HMX_DOT': 'f32'}, 261,
+        {'chain': 0, 'chain_pair': 0, 'usig': 1, 'upd_wps': 2, 'dot_bf': 0, 'moe_mfma': 0, 'host': 0},
+        {'head': (0, 13, 1, 2, 1), 'update': (0, 13, 0, 2, 1), 'stats': (0, 16, 0), 'apply': (0, 4, 1)}),
+    't13_K200_d68_v': (4000, 68, (4,), 200, 'v', {}, 262,
+        {'chain': 0, 'chain_pair': 0, 'usig': 0, 'upd_wps': 2, 'dot_bf': 0, 'moe_mfma': 0, 'host': 0},
+        {'head': (0, 13, 1, 2, 0), 'update': (0, 13, 0, 2, 0), 'stats': (0, 24, 0), 'apply': (0, 4, 2)}),
+    't13_K208_d64_v_c2': (4000, 64, (3, 2), 208, 'v', {}, 263,
+        {'chain': 0, 'chain_pair': 0, 'usig': 0, 'upd_wps': 2, 'dot_bf': 1, 'moe_mfma': 1, 'host': 0},
+        {'head': (1, 13, 1, 2, 0), 'update': (1, 13, 0, 2, 0), 'stats': (1, 7, 1), 'apply': (1, 4, 0)}),
+    't14_K209_d50_u_dotf32': (4000, 50, (4,), 209, 'u', {'HMX_DOT': 'f32'}, 264,
+        {'chain': 0, 'chain_pair': 0, 'usig': 1, 'upd_wps': 2, 'dot_bf': 0, 'moe_mfma': 0, 'host': 0},
+        {'head': (0, 14, 1, 2, 1), 'update': (0, 14, 0, 2, 1), 'stats': (0, 28, 0), 'apply': (0, 4, 1)}),
+    't14_K216_d100_v': (4000, 100, (4,), 216, 'v', {}, 265,
+        {'chain': 0, 'chain_pair': 0, 'usig': 0, 'upd_wps': 2, 'dot_bf': 1, 'moe_mfma': 0, 'host': 0},
+        {'head': (0, 14, 1, 2, 0), 'update': (0, 14, 0, 2, 0), 'stats': (0, 28, 0), 'apply': (0, 4, 2)}),
+    't14_K224_d24_v': (4000, 24, (4,), 224, 'v', {}, 266,
+        {'chain': 0, 'chain_pair': 0, 'usig': 0, 'upd_wps': 2, 'dot_bf': 1, 'moe_mfma': 1, 'host': 0},
+        {'head': (1, 14, 1, 2, 0), 'update': (1, 14, 0, 2, 0), 'stats': (1, 7, 1), 'apply': (1, 2, 0)}),
+    't14_K224_d96_u_c2': (4000, 96, (3, 2), 224, 'u', {}, 267,
+        {'chain': 0, 'chain_pair': 0, 'usig': 1, 'upd_wps': 2, 'dot_bf': 1, 'moe_mfma': 0, 'host': 0},
+        {'head': (1, 14, 1, 2, 1), 'update': (1, 14, 0, 2, 1), 'stats': (0, 32, 0), 'apply': (0, 4, 2)}),
+    't16_K225_d1_u': (4000, 1, (4,), 225, 'u', {}, 268,
+        {'chain': 0, 'chain_pair': 0, 'usig': 1, 'upd_wps': 2, 'dot_bf': 1, 'moe_mfma': 0, 'host': 0},
+        {'head': (1, 16, 1, 2, 1), 'update': (1, 16, 0, 2, 1), 'stats': (0, 4, 0), 'apply': (0, 4, 1)}),
+    't16_K232_d64_v': (4000, 64, (4,), 232, 'v', {}, 272,      # (the statistics without LDS shadows as two halves of 116 clusters: grid.y = 2)
+        {'chain': 0, 'chain_pair': 0, 'usig': 0, 'upd_wps': 2, 'dot_bf': 1, 'moe_mfma': 1, 'host': 0},
+        {'head': (1, 16, 1, 2, 0), 'update': (1, 16, 0, 2, 0), 'stats': (1, 8, 0), 'apply': (1, 4, 0)}),
+    't16_K241_d28_v_c2': (4000, 28, (3, 2), 241, 'v', {}, 269,
+        {'chain': 0, 'chain_pair': 0, 'usig': 0, 'upd_wps': 2, 'dot_bf': 1, 'moe_mfma': 0, 'host': 0},
+        {'head': (1, 16, 1, 2, 0), 'update': (1, 16, 0, 2, 0), 'stats': (0, 28, 0), 'apply': (0, 4, 1)}),
+    't16_K248_d128_v_c2': (4000, 128, (3, 2), 248, 'v', {}, 270,
+        {'chain': 0, 'chain_pair': 0, 'usig': 0, 'upd_wps': 2, 'dot_bf': 1, 'moe_mfma': 0, 'host': 0},
+        {'head': (0, 16, 1, 2, 0), 'update': (0, 16, 0, 2, 0), 'stats': (0, 32, 0), 'apply': (0, 4, 2)}),
+    't16_K256_d48_u_c2': (4000, 48, (3, 2), 256, 'u', {}, 271,
+        {'chain': 0, 'chain_pair': 0, 'usig': 1, 'upd_wps': 2, 'dot_bf': 1, 'moe_mfma': 1, 'host': 0},
+        {'head': (1, 16, 1, 2, 1), 'update': (1, 16, 0, 2, 1), 'stats': (1, 8, 1), 'apply': (1, 3, 0)}),
+}
+CASES += sorted(LATTICE)
 # the getters a case may claim (hmx_get scalars)
 PATH_GETTERS = ("chain", "chain_pair", "usig", "upd_wps", "dot_bf", "sold_carry", "shuffle_inv", "need_lorder", "objslots", "upd_contig", "moe_mfma",
                 "n_blocks", "cells_per_block")
@@ -221,6 +466,14 @@ def test_stages_match_the_spec(name, monkeypatch):
     if "max_kept" in path:
         assert info["max_kept"] <= path["max_kept"], msg
     assert (int(h._scalar("n_blocks")), int(h._scalar("cells_per_block"))) == (info["n_blocks"], info["cells_per_block"]), msg
+    if name in LATTICE:      # the instantiations that ran last are the ones the ledger credits the case with (tests/test_stage_ref_cpu.py holds the table to the plan)
+        credit = LATTICE[name][8]
+        for kind, want in credit.items():
+            ran = dict(zip(RIDGE_FIELDS if kind in ("stats", "apply") else LAUNCH_FIELDS, (int(v) for v in h._get("launch:" + kind))))
+            got = (ran["mfma"], ran["p0"], ran["p1"]) if kind in ("stats", "apply") else (ran["bf"], ran["nct"], ran["mode"], ran["wps"], ran["usig"])
+            assert got == want, (kind, ran, msg)
+        with pytest.raises(HarmonyError):
+            h._get("launch:" + ("update" if "chain" in credit else "chain"))
 
     # the keep decisions are comparable only away from the cutoff
     assert info["keep_margin"] >= KEEP_MARGIN, msg
@@ -247,16 +500,35 @@ LADDERS = {
     "wave_pair_chain": (60000, 200, (8, 64, 128), True, {"HMX_SOLD_CARRY": "1"}, 32, dict(chain=1, chain_pair=1, sold_carry=1)),
 }
 LADDER_ROUNDS = 5       # rounds 0..3 are one sort group, round 4 opens the next
+# The chain without R stores (k_tile MODE 5) at 1 .. 6 cluster tiles: two rounds at 6000 cells with the carry forced on (it never pays by itself below 100 000
+# cells); the first round of the second rung stores no R and is judged through what it hands to the second.  name -> (cells, clusters, PCs, levels, environment, seed, path)
+SMALL_LADDERS = {
+    "chain_1_tile_K16": (6000, 16, 50, (4,), {"HMX_SOLD_CARRY": "1"}, 41, dict(chain=1, chain_pair=0, sold_carry=1)),
+    "chain_2_tiles_K17": (6000, 17, 32, (4,), {"HMX_SOLD_CARRY": "1"}, 42, dict(chain=1, chain_pair=0, sold_carry=1)),
+    "chain_3_tiles_K40": (6000, 40, 64, (3, 2), {"HMX_SOLD_CARRY": "1"}, 43, dict(chain=1, chain_pair=0, sold_carry=1)),
+    "chain_4_tiles_K64": (6000, 64, 17, (4,), {"HMX_SOLD_CARRY": "1"}, 44, dict(chain=1, chain_pair=0, sold_carry=1)),
+    "chain_5_tiles_K65": (6000, 65, 50, (3, 2), {"HMX_SOLD_CARRY": "1"}, 45, dict(chain=1, chain_pair=0, sold_carry=1)),
+    "chain_6_tiles_K92": (6000, 92, 48, (4,), {"HMX_SOLD_CARRY": "1"}, 46, dict(chain=1, chain_pair=0, sold_carry=1)),
+}
+SMALL_LADDER_ROUNDS = 2
+
+
+def ladder_rounds(name):
+    return SMALL_LADDER_ROUNDS if name in SMALL_LADDERS else LADDER_ROUNDS
 
 
 def _ladder(name):
     """(Z, meta, vars_use, setup kwargs, environment, seed, path); epsilon_cluster = -1e9: the windowed check (iter > window_size) never ends a call"""
-    N, K, levels, nested, env, seed, path = LADDERS[name]
-    Z, meta, _ = synth(N, d=50, levels=levels, nested=nested, seed=seed)
+    if name in SMALL_LADDERS:
+        N, K, d, levels, env, seed, path = SMALL_LADDERS[name]
+        nested = False
+    else:
+        (N, K, levels, nested, env, seed, path), d = LADDERS[name], 50
+    Z, meta, _ = synth(N, d=d, levels=levels, nested=nested, seed=seed)
     return Z, meta, ["cov%d" % i for i in range(len(levels))], dict(nclust=K, options=harmony_options(epsilon_cluster=-1e9)), env, seed, path
 
 
-@pytest.mark.parametrize("name", sorted(LADDERS))
+@pytest.mark.parametrize("name", sorted(LADDERS) + sorted(SMALL_LADDERS))
 def test_round_ladder_matches_the_spec(name, monkeypatch):
     """H_m, m = 1..5: one cluster_cpp of m rounds from the same setup, seed and Y0; rung m = round m - 1 of H_m against the fp64 spec, from
     H_{m-1}'s stored R to H_m's own.  The counters must show that the rounds before the last really took the path under test.  Every one of
@@ -293,7 +565,7 @@ def test_round_ladder_matches_the_spec(name, monkeypatch):
     def probe(h):
         return {g: int(h._scalar(g)) for g in ("carried_rounds", "rounds_without_R", "chain_rounds", "chain", "chain_pair", "sold_carry", "shuffle_inv")}
 
-    rungs = run_ladder(make_handle, skw, Y0, order_of_round, rounds=LADDER_ROUNDS, probe=probe)
+    rungs = run_ladder(make_handle, skw, Y0, order_of_round, rounds=ladder_rounds(name), probe=probe)
     for rung in rungs:
         print("STAGE_SPEC", "ladder_%s_rung_%d" % (name, rung["m"]), json.dumps({"err": rung, "seconds": round(time.time() - t0, 1)}, default=str))
     for rung in rungs:

@@ -16,7 +16,10 @@ from helpers import synth  # noqa: E402
 from oracle.oracle import OracleHarmony  # noqa: E402
 from oracle.oracle import feistel_order  # noqa: E402
 from stage_check import phi_matrix, run_ladder, run_stages  # noqa: E402
-from test_gpu_stage_spec import LADDERS, PLAN_CASES, _case, _ladder  # noqa: E402  (the GPU cases: their claims are checked here first)
+import stage_lattice as lattice  # noqa: E402
+import test_gpu_kmeans as gpu_kmeans  # noqa: E402
+import test_gpu_stage_spec as gpu_spec  # noqa: E402
+from test_gpu_stage_spec import LADDERS, LATTICE, SMALL_LADDERS, PLAN_CASES, _case, _ladder  # noqa: E402  (the GPU cases: their claims are checked here first)
 from test_plan_cpu import plan  # noqa: E402
 
 BAR = 1e-5      # the oracle keeps R, O, E, Z, Y in fp32
@@ -159,7 +162,7 @@ def _plan_of(skw, env, monkeypatch):
     return p, Q
 
 
-@pytest.mark.parametrize("name", PLAN_CASES)
+@pytest.mark.parametrize("name", PLAN_CASES + sorted(LATTICE))
 def test_gpu_cases_claim_what_the_plan_gives(name, monkeypatch):
     """a later change of a threshold must not silently empty a case: its claimed path is the plan's, for its own B, Q and tile count"""
     Z, meta, var, kw, env, _seed, path = _case(name)
@@ -171,6 +174,13 @@ def test_gpu_cases_claim_what_the_plan_gives(name, monkeypatch):
     assert p["solve_on_device"] == 1 - path["host"]
     if "last_block" in path:
         assert N - (p["n_blocks"] - 1) * p["cells_per_block"] == path["last_block"]
+    if name in LATTICE:
+        # the instantiations the table credits the case with are the ledger's for the case's own design; its K is the one its name files it under
+        got, _bounds = ledger_of("stages", name)
+        credit = LATTICE[name][8]
+        assert {(("k_tile",) if kind in ("head", "update", "chain") else (kind,)) + tuple(v) for kind, v in credit.items()} == \
+            {v for v, kind in got.items() if kind not in ("seed", "lloyd")}, (credit, got)
+        assert ("chain" in credit) == bool(path["chain"]) and p["NCT"] == int(name[1:3]) and "K%d_" % skw["K"] in name
     if name == "o_blocks_63_carried":
         # the padded order with 63 * 63 keys stays inside int32, and the blocks inside lpair's 6 bits
         assert (p["nkeys"], p["npad"]) == (3969, N + 3969 * Q * 16) and p["npad"] < 2 ** 31 and p["n_blocks"] - 1 < 64
@@ -184,7 +194,7 @@ def test_gpu_cases_claim_what_the_plan_gives(name, monkeypatch):
         assert (p["nrep"], p["upd_threads"], p["upd_maxblocks"], p["upd_tpw"]) == (1, 256, 64, 3)
 
 
-@pytest.mark.parametrize("name", sorted(LADDERS))
+@pytest.mark.parametrize("name", sorted(LADDERS) + sorted(SMALL_LADDERS))
 def test_gpu_ladders_claim_what_the_plan_gives(name, monkeypatch):
     Z, meta, var, kw, env, _seed, path = _ladder(name)
     skw, _ = prepare_setup_args(Z, meta, var, **kw)
@@ -194,7 +204,7 @@ def test_gpu_ladders_claim_what_the_plan_gives(name, monkeypatch):
 
 
 @pytest.mark.parametrize("name", ["o_blocks_100", "o_blocks_64", "o_blocks_65", "o_blocks_1000_four_waves", "q_d68_fp32_on_the_chain",
-                                  "q_d76_fp32_on_the_chain"])
+                                  "q_d76_fp32_on_the_chain"] + sorted(LATTICE))
 def test_oracle_stages_match_the_spec_on_the_small_gpu_cases(name):
     """the small new GPU cases through the CPU oracle: the spec handles 63..1000 blocks and d = 68 / 76, and the cases' keep decisions sit away
     from the cutoff because of their data (everything they depend on but the library's own fp32 tables)"""
@@ -219,3 +229,80 @@ def test_oracle_round_ladder_matches_the_spec():
     for r in rungs:
         assert r["R"] <= BAR and r["argmax"] == 0 and max(r["O"], r["E"], r["obj"]) <= BAR, r
         assert r["first"] == rungs[0]["first"], r      # the oracle repeats itself bit for bit
+
+
+# ---- the coverage ledger (tests/stage_lattice.py): the cases between them launch every instantiation the plan reaches at small shapes --------------------------
+_ledger = {}
+
+
+def ledger_of(kind, name):
+    """(instantiations, loop bounds) of one stage-spec case, ladder or k-means case, for its own design"""
+    if (kind, name) not in _ledger:
+        if kind == "stages":
+            Z, meta, var, kw, env, _seed, _path = _case(name)
+            script = "stages"
+        elif kind == "ladder":
+            Z, meta, var, kw, env, _seed, _path = _ladder(name)
+            script = ("ladder", gpu_spec.ladder_rounds(name))
+        elif kind == "kmeans":
+            Z, meta, var, kw, env = gpu_kmeans.case_data(name)
+            script = "kmeans"
+        else:       # tests/test_gpu_parity2.py::test_kmeans_centers_headline_shape: (N, d, K)
+            Z, meta, _ = synth(name[0], d=name[1], levels=(10,), seed=9)
+            var, kw, env, script = "cov0", dict(nclust=name[2]), {}, "kmeans"
+        skw, _ = prepare_setup_args(Z, meta, var, **kw)
+        N, K, shape, items = lattice.shape_of(skw)
+        got, p = lattice.launches(N, K, shape, items, env, script)
+        assert got, (kind, name, p)
+        _ledger[(kind, name)] = (got, lattice.loop_bounds(got, p))
+    return _ledger[(kind, name)]
+
+
+def _older_cases():
+    return [("stages", n) for n in gpu_spec.CASES if n not in LATTICE and not n.endswith("_pushed")] + [("ladder", n) for n in sorted(LADDERS) + sorted(SMALL_LADDERS)]
+
+
+def ledger_of_existing_cases():
+    return set().union(*[set(ledger_of(*c)[0]) for c in _older_cases()])
+
+
+def bounds_of_existing_cases():
+    return set().union(*[ledger_of(*c)[1] for c in _older_cases()])
+
+
+# Instantiations of the envelope that no case can reach below 100 000 cells, each with the plan expression that keeps it out of reach.  At most 5 % of the envelope.
+EXCLUSIONS = {}
+
+
+def test_the_cases_launch_every_instantiation_the_envelope_reaches():
+    """Every kernel instantiation the plan reaches across the envelope (tests/stage_lattice.py: K = 1 .. 256, 17 values of d, both sigma forms, one and two covariates,
+    4000 and 6000 cells, with and without HMX_CHAIN=0, two rounds with the carry forced on) is launched by a stage-spec case, a ladder or a k-means case -- each for its
+    own B, C, Q, tile counts and block partition --, and so held to an fp64 spec on the GPU.  What the cases launch beyond the envelope (shapes only many cells reach) is printed."""
+    reach, _ = lattice.envelope()
+    cases = _older_cases() + [("stages", n) for n in sorted(LATTICE)] + [("kmeans", n) for n in sorted(gpu_kmeans.CASES)] + \
+        [("kmeans_old", (100000, 50, 100)), ("kmeans_old", (20000, 128, 256))]
+    held, bounds = {}, set()
+    for c in cases:
+        got, b = ledger_of(*c)
+        bounds |= b
+        for v in got:
+            held.setdefault(v, []).append(c)
+    print("envelope: %d instantiations; cases: %d, launching %d" % (len(reach), len(cases), len(held)))
+    print("exclusions (%d):" % len(EXCLUSIONS))
+    for v, why in sorted(EXCLUSIONS.items()):
+        print("  ", v, why)
+    print("launched beyond the envelope:", sorted(set(held) - set(reach)))
+    assert len(EXCLUSIONS) <= 0.05 * len(reach) and set(EXCLUSIONS) <= set(reach) and not set(EXCLUSIONS) & set(held)
+    missing = sorted(set(reach) - set(held) - set(EXCLUSIONS))
+    assert not missing, [(v, reach[v]) for v in missing]
+    assert set(held) & set(reach) == set(reach) - set(EXCLUSIONS)
+    # the seeding race and Lloyd: every instantiation by a k-means case of its own (centres judged, not only handed on)
+    km = {v for v, cs in held.items() if any(c[0] == "kmeans" for c in cs)}
+    assert {v for v in reach if v == ("k_lloyd",) or (v[0] == "k_tile" and v[3] in (2, 3))} <= km
+    assert {("k_tile", 1, n, 2, 3, 0) for n in (5, 6, 7)} <= km          # (the three-wave Lloyd: beyond the envelope, more than 1024 static tiles)
+    # the chain without R stores at 1 .. 7 cluster tiles by a ladder
+    assert {("k_tile", 1, n, 5, 2, 1) for n in range(1, 8)} <= {v for v, cs in held.items() if any(c[0] == "ladder" for c in cs)}
+    # the loop bounds of d, in each build that the plan admits them in: NT4 = 0 .. 8, tail = 0 .. 3, NS2 = 1 .. 4
+    want = lattice.admitted_loop_bounds()
+    assert {(bf, f, v) for bf in (0, 1) for f, vs in (("NT4", range(9)), ("tail", range(4)), ("NS2", range(1, 5))) for v in vs} == want
+    assert want <= bounds, sorted(want - bounds)

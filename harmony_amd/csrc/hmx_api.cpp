@@ -366,6 +366,7 @@ int hmx_moe_correct_ridge(hmx_ctx* ctx) {  // src/harmony.cpp:345-638
 #include "hmx_api_metrics.inc"
 #include "hmx_api_silhouette.inc"
 #include "hmx_api_confidence.inc"
+#include "hmx_api_csr.inc"
 #include "hmx_api_project.inc"
 #include "hmx_api_pca.inc"
 #include "hmx_api_groups.inc"

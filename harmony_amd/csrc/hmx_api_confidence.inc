@@ -102,18 +102,16 @@ int hmx_reference_moments(hmx_ctx* ctx, int32_t space, double* mean, double* cov
   {
     CallBufs B;
     float* dc; Item* dch; int* dfold; double* dres;
-    HIPCHK(B.get(&dc, c.size())); HIPCHK(B.get(&dch, chunks.size())); HIPCHK(B.get(&dfold, 2));
+    HIPCHK(B.put(&dc, c.data(), c.size(), ctx->L.stream)); HIPCHK(B.put(&dch, chunks.data(), chunks.size(), ctx->L.stream));
+    HIPCHK(B.put(&dfold, fold, 2, ctx->L.stream));
     HIPCHK(B.get(&P.part, (size_t)P.nchunks * total)); HIPCHK(B.get(&dres, total));
-    HIPCHK(hipMemcpyAsync(dc, c.data(), c.size() * sizeof(float), hipMemcpyHostToDevice, ctx->L.stream));
-    HIPCHK(hipMemcpyAsync(dch, chunks.data(), chunks.size() * sizeof(Item), hipMemcpyHostToDevice, ctx->L.stream));
-    HIPCHK(hipMemcpyAsync(dfold, fold, sizeof(fold), hipMemcpyHostToDevice, ctx->L.stream));
     P.c = dc; P.chunks = dch;
     hipError_t e = hipSuccess;
     if (P.nchunks) { l_conf_moments(ctx->L, P); e = hipGetLastError(); }
     if (e == hipSuccess) { l_query_fold(ctx->L, P.part, dfold, 1, (int)total, dres); e = hipGetLastError(); }
     int st = 0;
     if (e == hipSuccess) st = allreduce(ctx, dres, (int64_t)total, 1);      // sharded handle: the global sums on every rank
-    if (e == hipSuccess && !st) e = hipMemcpyAsync(M.data(), dres, total * sizeof(double), hipMemcpyDeviceToHost, ctx->L.stream);
+    if (e == hipSuccess && !st) e = download(M.data(), dres, total, ctx->L.stream);
     const hipError_t es = hipStreamSynchronize(ctx->L.stream);      // (the buffers are released below: nothing may still use them)
     if (st) return st;
     if (e != hipSuccess || es != hipSuccess) return fail(ctx, HMX_ERR_DEVICE, std::string("reference moments: ") + hipGetErrorString(e != hipSuccess ? e : es));
@@ -192,16 +190,14 @@ int hmx_mapping_confidence(hmx_ctx* ctx, int32_t space, const double* mean, cons
   P.Zs = space == HMX_SPACE_CORR ? D.Zc : D.Zo;
   P.perm = D.perm;
   float* dU; float* dmu;
-  HIPCHK(B.get(&dU, U.size())); HIPCHK(B.get(&dmu, mu.size()));
+  HIPCHK(B.put(&dU, U.data(), U.size(), ctx->L.stream)); HIPCHK(B.put(&dmu, mu.data(), mu.size(), ctx->L.stream));
   HIPCHK(B.get(&P.score, (size_t)Nq));
   P.dist = nullptr;
   if (dist) HIPCHK(B.get(&P.dist, (size_t)Nq * K));
-  HIPCHK(hipMemcpyAsync(dU, U.data(), U.size() * sizeof(float), hipMemcpyHostToDevice, ctx->L.stream));
-  HIPCHK(hipMemcpyAsync(dmu, mu.data(), mu.size() * sizeof(float), hipMemcpyHostToDevice, ctx->L.stream));
   P.U = dU; P.mu = dmu;
   l_conf_score(ctx->L, P); KCHK();
-  HIPCHK(hipMemcpyAsync(score, P.score, (size_t)Nq * sizeof(double), hipMemcpyDeviceToHost, ctx->L.stream));
-  if (dist) HIPCHK(hipMemcpyAsync(dist, P.dist, (size_t)Nq * K * sizeof(float), hipMemcpyDeviceToHost, ctx->L.stream));
+  HIPCHK(download(score, P.score, (size_t)Nq, ctx->L.stream));
+  if (dist) HIPCHK(download(dist, P.dist, (size_t)Nq * K, ctx->L.stream));
   HIPCHK(hipStreamSynchronize(ctx->L.stream));
   ctx->timers["mapping_confidence"] = now_ms() - t0;
   return 0;

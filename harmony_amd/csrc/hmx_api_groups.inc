@@ -1,7 +1,6 @@
-// hmx_api_groups.inc -- part of hmx_api.cpp (included there, ONE translation unit, behind hmx_api_pca.inc whose uploads and flag check it uses,
-// and hmx_api_project.inc's count-matrix checks, slabs and sweep): hmx_gene_stats_grouped (include/harmony_mi355x_groups.h; DESIGN "Gene
-// statistics per group").  Kernel: k_gene_stats_grouped in hmx_pca.hip; the work list: hmx_group_plan.h.  The call leaves nothing on the handle
-// but the timer.
+// hmx_api_groups.inc -- part of hmx_api.cpp (included there, ONE translation unit): hmx_gene_stats_grouped (include/harmony_mi355x_groups.h;
+// DESIGN "Gene statistics per group").  Kernel: k_gene_stats_grouped in hmx_pca.hip; the work list: hmx_group_plan.h.  The count matrix's
+// checks, slabs, sweep and fixed-point steps are the count-matrix seam's (hmx_api_csr.inc).  The call leaves nothing on the handle but the timer.
 
 extern "C" {
 
@@ -21,47 +20,42 @@ int hmx_gene_stats_grouped(hmx_ctx* ctx, int64_t N, int32_t G_all, const int64_t
   // the slabs csr_sweep will cut (a pure function of indptr and the cap), then the chunks of every slab, once
   std::vector<int64_t> slab{0, N};
   if (csr_location == HMX_HOST) {
-    const int64_t cap_bytes = ctx->project_slab_bytes > 0 ? ctx->project_slab_bytes : PROJ_SLAB_BYTES;
     slab.assign(1, 0);
-    for (const ProjSlab& s : proj_slabs(indptr, N, std::max<int64_t>(1, cap_bytes / (4 + esz)))) slab.push_back(s.row1);
+    for (const CsrSlab& s : csr_slabs(indptr, N, csr_slab_cap(ctx, esz))) slab.push_back(s.row1);
   }
   GroupPlan plan;
   int64_t bad_cell = 0;
   if (group_plan(labels, N, B, slab.data(), (int64_t)slab.size() - 1, GROUP_CHUNK, plan, &bad_cell))
     return fail(ctx, HMX_ERR_ARG, "a label is outside [-1, B) (cell " + std::to_string(bad_cell) + ")");
   CHK(call_device(ctx));
-  // the steps of hmx_gene_stats, from the WHOLE N: group sums and ungrouped sums are multiples of the same step
-  const float ymax = totals ? 89.0f : (float)(1.001 * std::log1p(scale));
-  const int F1 = std::min(40, (int)std::floor(62.0 - std::log2((double)N * ymax)));
-  const int F2 = std::min(40, (int)std::floor(62.0 - std::log2((double)N * ymax * ymax)));
+  const GeneSteps T = gene_steps(N, scale, totals != nullptr);      // the steps of hmx_gene_stats
+  const int F1 = T.F1, F2 = T.F2;
   CallBufs bufs;
   GroupStatDev Q{};
   PcaStatDev& S = Q.S;
-  CHK(pca_common(ctx, bufs, S.C, N, G_all, data_dtype, scale, totals));
+  CHK(csr_uploads(ctx, bufs, S.C, N, G_all, data_dtype, scale, totals));
   hipStream_t st = ctx->L.stream;
   const size_t cells = (size_t)B * G_all;
   unsigned long long* acc; int* dperm; GroupChunk* dchunks;
-  HIPCHK(bufs.get(&acc, 3 * cells));
-  HIPCHK(bufs.get(&dperm, plan.perm.size()));
-  HIPCHK(bufs.get(&dchunks, plan.chunks.size()));
-  HIPCHK(hipMemsetAsync(acc, 0, 3 * cells * sizeof(unsigned long long), st));
-  if (!plan.perm.empty()) HIPCHK(hipMemcpyAsync(dperm, plan.perm.data(), plan.perm.size() * sizeof(int), hipMemcpyHostToDevice, st));
-  if (!plan.chunks.empty()) HIPCHK(hipMemcpyAsync(dchunks, plan.chunks.data(), plan.chunks.size() * sizeof(GroupChunk), hipMemcpyHostToDevice, st));
-  S.ymax = ymax; S.q1 = std::ldexp(1.0, F1); S.q2 = std::ldexp(1.0, F2); S.s1 = acc; S.s2 = acc + cells; S.n = acc + 2 * cells;
+  HIPCHK(bufs.get(&acc, 3 * cells)); HIPCHK(bufs.get(&dperm, plan.perm.size())); HIPCHK(bufs.get(&dchunks, plan.chunks.size()));
+  HIPCHK(zero_fill(acc, 3 * cells, st));
+  HIPCHK(upload(dperm, plan.perm.data(), plan.perm.size(), st));
+  HIPCHK(upload(dchunks, plan.chunks.data(), plan.chunks.size(), st));
+  S.ymax = T.ymax; S.q1 = std::ldexp(1.0, F1); S.q2 = std::ldexp(1.0, F2); S.s1 = acc; S.s2 = acc + cells; S.n = acc + 2 * cells;
   Q.perm = dperm;
   bool cut_ok = true;      // every launch found its slab in the table cut above
   CHK(csr_sweep(ctx, bufs, N, indptr, indices, data, esz, csr_location, "gene_stats_grouped",
-                [&](const long long* ptr, long long base, long long nnz, const int* idx, const void* val, long long nrows, long long row0) {
-                  S.C.indptr = ptr; S.C.base = base; S.C.nnz = nnz; S.C.indices = idx; S.C.data = val; S.C.nrows = nrows; S.C.row0 = row0;
-                  const size_t s = (size_t)(std::lower_bound(slab.begin(), slab.end(), (int64_t)row0) - slab.begin());      // the slab that starts at row0
-                  if (s + 1 >= slab.size() || slab[s] != row0 || slab[s + 1] != row0 + nrows) { cut_ok = false; return; }
+                [&](const CsrRows& R) {
+                  R.into(S.C);
+                  const size_t s = (size_t)(std::lower_bound(slab.begin(), slab.end(), (int64_t)R.row0) - slab.begin());      // the slab that starts at row0
+                  if (s + 1 >= slab.size() || slab[s] != R.row0 || slab[s + 1] != R.row0 + R.nrows) { cut_ok = false; return; }
                   Q.chunks = dchunks + plan.first[s]; Q.nchunks = plan.first[s + 1] - plan.first[s];
                   l_gene_stats_grouped(Q, st);
                 }));
   if (!cut_ok) return fail(ctx, HMX_ERR_STATE, "gene_stats_grouped: the sweep's slabs are not the ones the chunks were cut for");
   std::vector<unsigned long long> h(3 * cells);
-  HIPCHK(hipMemcpyAsync(h.data(), acc, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-  CHK(pca_flag(ctx, S.C));
+  HIPCHK(download(h.data(), acc, h.size(), st));
+  CHK(csr_flag(ctx, S.C));
   for (size_t c = 0; c < cells; c++) {
     s1[c] = std::ldexp((double)h[c], -F1);
     s2[c] = std::ldexp((double)h[cells + c], -F2);

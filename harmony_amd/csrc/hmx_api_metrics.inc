@@ -1,32 +1,6 @@
 // hmx_api_metrics.inc -- part of hmx_api.cpp (included there, ONE translation unit): hmx_knn, hmx_lisi and hmx_compute_lisi
 // (include/harmony_mi355x_metrics.h; DESIGN "Scoring an integration").  Kernels: hmx_knn.hip.  The calls keep no state on the handle
-// but the timers: every device buffer lives for one call (hmx_api_call.inc).
-
-namespace {
-
-// how the data rows are split over grid.y: one chunk when the query tiles alone fill the device, else enough chunks for ~512 workgroups,
-// each a multiple of the slab and at least 2 k rows long
-void knn_plan(KnnDev& P) {
-  const int64_t tiles = (P.Nq + KNN_QROWS - 1) / KNN_QROWS;
-  const int64_t want = std::max<int64_t>(1, std::min<int64_t>(512 / tiles, 512));
-  int64_t chunk = (P.N + want - 1) / want;
-  chunk = std::max<int64_t>(chunk, 2 * P.k);
-  chunk = (chunk + KNN_SLAB - 1) / KNN_SLAB * KNN_SLAB;
-  P.chunk = chunk;
-  P.nchunks = (int)((P.N + chunk - 1) / chunk);
-}
-
-// the search itself on device rows; idx / dist: device buffers [Nq][k]
-int knn_device(hmx_ctx* ctx, CallBufs& B, KnnDev P) {
-  P.NG = (P.zs + 15) / 16;
-  knn_plan(P);
-  P.part = nullptr;
-  if (P.nchunks > 1) HIPCHK(B.get(&P.part, (size_t)P.Nq * P.nchunks * P.k));
-  l_knn(ctx->L, P); KCHK();
-  return 0;
-}
-
-}  // namespace
+// but the timers: every device buffer lives for one call, and the search is the call seam's (hmx_api_call.inc).
 
 extern "C" {
 
@@ -63,8 +37,8 @@ int hmx_knn(hmx_ctx* ctx, const void* X, int32_t x_dtype, int32_t x_location, in
   if (out_location == HMX_HOST) { HIPCHK(B.get(&P.idx, cnt)); HIPCHK(B.get(&P.dist, cnt)); }
   CHK(knn_device(ctx, B, P));
   if (out_location == HMX_HOST) {
-    HIPCHK(hipMemcpyAsync(idx, P.idx, cnt * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->L.stream));
-    HIPCHK(hipMemcpyAsync(dist, P.dist, cnt * sizeof(float), hipMemcpyDeviceToHost, ctx->L.stream));
+    HIPCHK(download(idx, P.idx, cnt, ctx->L.stream));
+    HIPCHK(download(dist, P.dist, cnt, ctx->L.stream));
   }
   HIPCHK(hipStreamSynchronize(ctx->L.stream));
   ctx->timers["knn"] = now_ms() - t0;
@@ -87,12 +61,10 @@ int hmx_lisi(hmx_ctx* ctx, const int32_t* idx, const float* dist, int64_t Nq, in
   CallBufs B;
   int* didx; float* ddist; int* dlab; double* dout;
   const size_t cnt = (size_t)Nq * m;
-  HIPCHK(B.get(&didx, cnt)); HIPCHK(B.get(&ddist, cnt)); HIPCHK(B.get(&dlab, (size_t)n_cols * N)); HIPCHK(B.get(&dout, (size_t)Nq * n_cols));
-  HIPCHK(hipMemcpyAsync(didx, idx, cnt * sizeof(int32_t), hipMemcpyHostToDevice, ctx->L.stream));
-  HIPCHK(hipMemcpyAsync(ddist, dist, cnt * sizeof(float), hipMemcpyHostToDevice, ctx->L.stream));
-  HIPCHK(hipMemcpyAsync(dlab, labels, (size_t)n_cols * N * sizeof(int32_t), hipMemcpyHostToDevice, ctx->L.stream));
+  HIPCHK(B.put(&didx, idx, cnt, ctx->L.stream)); HIPCHK(B.put(&ddist, dist, cnt, ctx->L.stream));
+  HIPCHK(B.put(&dlab, labels, (size_t)n_cols * N, ctx->L.stream)); HIPCHK(B.get(&dout, (size_t)Nq * n_cols));
   l_lisi(ctx->L, didx, ddist, Nq, m, dlab, N, n_cols, perplexity, dout); KCHK();
-  HIPCHK(hipMemcpyAsync(out, dout, (size_t)Nq * n_cols * sizeof(double), hipMemcpyDeviceToHost, ctx->L.stream));
+  HIPCHK(download(out, dout, (size_t)Nq * n_cols, ctx->L.stream));
   HIPCHK(hipStreamSynchronize(ctx->L.stream));
   ctx->timers["lisi"] = now_ms() - t0;
   return 0;
@@ -113,23 +85,14 @@ int hmx_compute_lisi(hmx_ctx* ctx, const void* X, int32_t x_dtype, int32_t x_loc
   CHK(call_device(ctx));
   const double t0 = now_ms();
   CallBufs B;
-  KnnDev P{};
-  P.zs = (d + 3) / 4 * 4; P.k = m; P.excl = 1; P.N = P.Nq = N;
-  float* xr; float* xn;
-  CHK(score_rows(ctx, B, X, x_dtype, x_location, N, d, P.zs, &xr, &xn));
-  P.X = P.Q = xr; P.xn = P.qn = xn;
   int* dlab; double* dout;
-  HIPCHK(B.get(&P.idx, (size_t)N * m)); HIPCHK(B.get(&P.dist, (size_t)N * m));
-  HIPCHK(B.get(&dlab, (size_t)n_cols * N)); HIPCHK(B.get(&dout, (size_t)N * n_cols));
-  HIPCHK(hipMemcpyAsync(dlab, labels, (size_t)n_cols * N * sizeof(int32_t), hipMemcpyHostToDevice, ctx->L.stream));
-  CHK(knn_device(ctx, B, P));
+  HIPCHK(B.put(&dlab, labels, (size_t)n_cols * N, ctx->L.stream)); HIPCHK(B.get(&dout, (size_t)N * n_cols));
+  KnnLists K;
+  CHK(knn_front(ctx, B, t0, X, x_dtype, x_location, N, d, m, nullptr, nullptr, K));
+  l_lisi(ctx->L, K.idx, K.dist, N, m, dlab, N, n_cols, perplexity, dout); KCHK();
+  HIPCHK(download(out, dout, (size_t)N * n_cols, ctx->L.stream));
   HIPCHK(hipStreamSynchronize(ctx->L.stream));
-  const double t1 = now_ms();
-  l_lisi(ctx->L, P.idx, P.dist, N, m, dlab, N, n_cols, perplexity, dout); KCHK();
-  HIPCHK(hipMemcpyAsync(out, dout, (size_t)N * n_cols * sizeof(double), hipMemcpyDeviceToHost, ctx->L.stream));
-  HIPCHK(hipStreamSynchronize(ctx->L.stream));
-  ctx->timers["knn"] = t1 - t0;
-  ctx->timers["lisi"] = now_ms() - t1;
+  ctx->timers["lisi"] = now_ms() - K.t1;
   return 0;
 }
 

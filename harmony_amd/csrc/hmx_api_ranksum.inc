@@ -1,7 +1,7 @@
-// hmx_api_ranksum.inc -- part of hmx_api.cpp (included there, ONE translation unit, behind hmx_api_groups.inc; it uses hmx_api_pca.inc's uploads and
-// flag check and hmx_api_project.inc's count-matrix checks and sweep): hmx_rank_sums (include/harmony_mi355x_ranksum.h; DESIGN "Rank sums per
-// group").  Kernels: hmx_ranksum.hip; the plan: hmx_ranksum_plan.h.  The call leaves nothing on the handle but its timers and the number of
-// gene blocks it ran ("ranksum_blocks").
+// hmx_api_ranksum.inc -- part of hmx_api.cpp (included there, ONE translation unit): hmx_rank_sums (include/harmony_mi355x_ranksum.h; DESIGN
+// "Rank sums per group").  Kernels: hmx_ranksum.hip; the plan: hmx_ranksum_plan.h.  The count matrix's checks, sweep and gene map are the
+// count-matrix seam's (hmx_api_csr.inc).  The call leaves nothing on the handle but its timers and the number of gene blocks it ran
+// ("ranksum_blocks").
 
 namespace {
 constexpr int64_t RANKSUM_LIST_BYTES = (int64_t)8 << 30;      // a gene block's list and second buffer (the "ranksum_list_bytes" lab field overrides it)
@@ -21,17 +21,8 @@ int hmx_rank_sums(hmx_ctx* ctx, int64_t N, int32_t G_all, const int64_t* indptr,
   if (G <= 0) return fail(ctx, HMX_ERR_ARG, "at least one selected gene");
   if (!gene_slot && G != G_all) return fail(ctx, HMX_ERR_ARG, "a null gene_slot selects every gene: G must be G_all");
   if (B > 4096 || (int64_t)B * G > ((int64_t)1 << 25)) return fail(ctx, HMX_ERR_LIMIT, "supported envelope: B <= 4096, B G <= 2^25");
-  if (gene_slot) {
-    std::vector<char> taken((size_t)G, 0);
-    for (int32_t g = 0; g < G_all; g++) {
-      const int32_t j = gene_slot[g];
-      if (j < -1 || j >= G) return fail(ctx, HMX_ERR_ARG, "gene_slot[" + std::to_string(g) + "] = " + std::to_string(j) + " is outside -1 .. G - 1");
-      if (j >= 0) {
-        if (taken[(size_t)j]) return fail(ctx, HMX_ERR_ARG, "gene_slot maps two genes to output row " + std::to_string(j));
-        taken[(size_t)j] = 1;
-      }
-    }
-  }
+  std::vector<char> taken;
+  if (gene_slot) CHK(gene_slot_check(ctx, gene_slot, G_all, G, "gene_slot", "genes to output row", taken));
   std::vector<int64_t> obs((size_t)B, 0);
   int64_t Nk = 0;
   for (int64_t i = 0; i < N; i++) {
@@ -47,31 +38,23 @@ int hmx_rank_sums(hmx_ctx* ctx, int64_t N, int32_t G_all, const int64_t* indptr,
   const size_t cells = (size_t)B * G;
   CallBufs bufs;
   RankSweepDev S{};
-  CHK(pca_common(ctx, bufs, S.C, N, G_all, data_dtype, scale, totals));
+  CHK(csr_uploads(ctx, bufs, S.C, N, G_all, data_dtype, scale, totals));
   int* dlabels; int* dslot = nullptr; unsigned long long* dcount;
-  HIPCHK(bufs.get(&dlabels, (size_t)N)); HIPCHK(bufs.get(&dcount, (size_t)G));
-  HIPCHK(hipMemcpyAsync(dlabels, labels, (size_t)N * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemsetAsync(dcount, 0, (size_t)G * sizeof(unsigned long long), st));
-  if (gene_slot) {
-    HIPCHK(bufs.get(&dslot, (size_t)G_all));
-    HIPCHK(hipMemcpyAsync(dslot, gene_slot, (size_t)G_all * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  }
+  HIPCHK(bufs.put(&dlabels, labels, (size_t)N, st)); HIPCHK(bufs.get(&dcount, (size_t)G));
+  HIPCHK(zero_fill(dcount, (size_t)G, st));
+  if (gene_slot) HIPCHK(bufs.put(&dslot, gene_slot, (size_t)G_all, st));
   S.C.slot = dslot; S.C.G = G; S.labels = dlabels; S.count = dcount;
   auto sweep = [&](bool fill) {
     CallBufs staging;      // (a pass returns with its streams drained: a sweep's staging sets are gone before the next one allocates its own)
     return csr_sweep(ctx, staging, N, indptr, indices, data, esz, csr_location, "rank_sums",
-                     [&](const long long* ptr, long long base, long long nnz, const int* idx, const void* val, long long nrows, long long row0) {
-                       S.C.indptr = ptr; S.C.base = base; S.C.nnz = nnz; S.C.indices = idx; S.C.data = val; S.C.nrows = nrows; S.C.row0 = row0;
-                       l_rank_sweep(S, fill, st);
-                     });
+                     [&](const CsrRows& R) { R.into(S.C); l_rank_sweep(S, fill, st); });
   };
   // ---- the count sweep (it validates the matrix), then the plan
   S.j0 = 0; S.j1 = G;
   CHK(sweep(false));
   std::vector<int64_t> count((size_t)G);
-  static_assert(sizeof(unsigned long long) == sizeof(int64_t), "the counts are read as they are");
-  HIPCHK(hipMemcpyAsync(count.data(), dcount, (size_t)G * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-  CHK(pca_flag(ctx, S.C));
+  HIPCHK(download(count.data(), dcount, (size_t)G, st));      // (the counts are read as they are)
+  CHK(csr_flag(ctx, S.C));
   const double t_count = now_ms();
   for (int32_t j = 0; j < G; j++)
     if (count[(size_t)j] > Nk) return fail(ctx, HMX_ERR_ARG, "a row stores a gene more than once (output row " + std::to_string(j) + ")");
@@ -84,17 +67,14 @@ int hmx_rank_sums(hmx_ctx* ctx, int64_t N, int32_t G_all, const int64_t* indptr,
   for (int32_t j = 0; j < G; j++) radix = radix || plan.path[(size_t)j] == RANKSUM_RADIX;
   long long* dseg; unsigned* dcursor; int* dorder; unsigned* dnext; unsigned long long* dlist; unsigned long long* dother;
   unsigned long long* drank; unsigned* dnpos; unsigned long long* dtie;
-  HIPCHK(bufs.get(&dseg, (size_t)G + 1)); HIPCHK(bufs.get(&dcursor, (size_t)G)); HIPCHK(bufs.get(&dorder, plan.order.size()));
+  HIPCHK(bufs.put(&dseg, plan.seg.data(), (size_t)G + 1, st)); HIPCHK(bufs.get(&dcursor, (size_t)G)); HIPCHK(bufs.put(&dorder, plan.order.data(), plan.order.size(), st));
   HIPCHK(bufs.get(&dnext, (size_t)nblocks)); HIPCHK(bufs.get(&dlist, (size_t)plan.max_entries)); HIPCHK(bufs.get(&dother, radix ? (size_t)plan.max_entries : 1));
   HIPCHK(bufs.get(&drank, cells)); HIPCHK(bufs.get(&dnpos, cells)); HIPCHK(bufs.get(&dtie, 2 * (size_t)G));
-  static_assert(sizeof(long long) == sizeof(int64_t), "the segments are uploaded as they are");
-  HIPCHK(hipMemcpyAsync(dseg, plan.seg.data(), ((size_t)G + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
-  if (!plan.order.empty()) HIPCHK(hipMemcpyAsync(dorder, plan.order.data(), plan.order.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemsetAsync(dcursor, 0, (size_t)G * sizeof(unsigned), st));
-  HIPCHK(hipMemsetAsync(dnext, 0, (size_t)nblocks * sizeof(unsigned), st));
-  HIPCHK(hipMemsetAsync(drank, 0, cells * sizeof(unsigned long long), st));
-  HIPCHK(hipMemsetAsync(dnpos, 0, cells * sizeof(unsigned), st));
-  HIPCHK(hipMemsetAsync(dtie, 0, 2 * (size_t)G * sizeof(unsigned long long), st));
+  HIPCHK(zero_fill(dcursor, (size_t)G, st));
+  HIPCHK(zero_fill(dnext, (size_t)nblocks, st));
+  HIPCHK(zero_fill(drank, cells, st));
+  HIPCHK(zero_fill(dnpos, cells, st));
+  HIPCHK(zero_fill(dtie, 2 * (size_t)G, st));
   S.seg = dseg; S.cursor = dcursor; S.list = dlist;
   RankSortDev R{};
   R.seg = dseg; R.list = dlist; R.other = dother; R.B = B; R.G = G; R.Nk = Nk; R.rank2 = drank; R.npos = dnpos; R.tie3 = dtie;
@@ -105,7 +85,7 @@ int hmx_rank_sums(hmx_ctx* ctx, int64_t N, int32_t G_all, const int64_t* indptr,
     const int64_t entries = plan.seg[(size_t)j1] - plan.seg[(size_t)j0];
     if (entries <= 0) continue;
     const double ta = now_ms();
-    HIPCHK(hipMemsetAsync(dlist, 0, (size_t)entries * sizeof(unsigned long long), st));      // (a host matrix that changes between two sweeps leaves defined entries)
+    HIPCHK(zero_fill(dlist, (size_t)entries, st));      // (a host matrix that changes between two sweeps leaves defined entries)
     S.j0 = j0; S.j1 = j1; S.base = plan.seg[(size_t)j0]; S.entries = entries;
     CHK(sweep(true));
     HIPCHK(hipStreamSynchronize(st));      // (a device-resident sweep returns with its kernel queued: the stage timers are split here)
@@ -118,10 +98,10 @@ int hmx_rank_sums(hmx_ctx* ctx, int64_t N, int32_t G_all, const int64_t* indptr,
   }
   std::vector<unsigned long long> hrank(cells), htie(2 * (size_t)G);
   std::vector<unsigned> hnpos(cells);
-  HIPCHK(hipMemcpyAsync(hrank.data(), drank, cells * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(hnpos.data(), dnpos, cells * sizeof(unsigned), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(htie.data(), dtie, htie.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-  CHK(pca_flag(ctx, S.C));
+  HIPCHK(download(hrank.data(), drank, cells, st));
+  HIPCHK(download(hnpos.data(), dnpos, cells, st));
+  HIPCHK(download(htie.data(), dtie, htie.size(), st));
+  CHK(csr_flag(ctx, S.C));
   // ---- the zeros' share: a cell without a positive entry of gene g has the doubled midrank z_g + 1, z_g = N_k - P_g
   for (int32_t b = 0; b < B; b++) {
     n_obs[b] = obs[(size_t)b];

@@ -74,18 +74,16 @@ int hmx_silhouette(hmx_ctx* ctx, const void* X, int32_t x_dtype, int32_t x_locat
   float* xr; float* xn;
   CHK(score_rows(ctx, B, X, x_dtype, x_location, N, d, P.zs, &xr, &xn));
   int* dsrc; SilTile* dtile; int* dgrange; float* sr; float* sn;
-  HIPCHK(B.get(&dsrc, Y.src.size())); HIPCHK(B.get(&dtile, Y.tile.size())); HIPCHK(B.get(&dgrange, Y.grange.size()));
+  HIPCHK(B.put(&dsrc, Y.src.data(), Y.src.size(), ctx->L.stream)); HIPCHK(B.put(&dtile, Y.tile.data(), Y.tile.size(), ctx->L.stream));
+  HIPCHK(B.put(&dgrange, Y.grange.data(), Y.grange.size(), ctx->L.stream));
   HIPCHK(B.get(&sr, (size_t)P.Np * P.zs)); HIPCHK(B.get(&sn, (size_t)P.Np));
   HIPCHK(B.get(&P.s, (size_t)N)); HIPCHK(B.get(&P.a, (size_t)N)); HIPCHK(B.get(&P.b, (size_t)N));
-  HIPCHK(hipMemcpyAsync(dsrc, Y.src.data(), Y.src.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->L.stream));
-  HIPCHK(hipMemcpyAsync(dtile, Y.tile.data(), Y.tile.size() * sizeof(SilTile), hipMemcpyHostToDevice, ctx->L.stream));
-  HIPCHK(hipMemcpyAsync(dgrange, Y.grange.data(), Y.grange.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->L.stream));
   l_sil_gather(ctx->L, xr, xn, dsrc, P.Np, P.zs, sr, sn); KCHK();
   P.X = sr; P.xn = sn; P.src = dsrc; P.tile = dtile; P.grange = dgrange;
   l_silhouette(ctx->L, P); KCHK();
-  HIPCHK(hipMemcpyAsync(s, P.s, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, ctx->L.stream));
-  if (a) HIPCHK(hipMemcpyAsync(a, P.a, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, ctx->L.stream));
-  if (b) HIPCHK(hipMemcpyAsync(b, P.b, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, ctx->L.stream));
+  HIPCHK(download(s, P.s, (size_t)N, ctx->L.stream));
+  if (a) HIPCHK(download(a, P.a, (size_t)N, ctx->L.stream));
+  if (b) HIPCHK(download(b, P.b, (size_t)N, ctx->L.stream));
   HIPCHK(hipStreamSynchronize(ctx->L.stream));
   ctx->timers["silhouette"] = now_ms() - t0;
   return 0;

@@ -1,6 +1,7 @@
-// hmx_api_snn.inc -- part of hmx_api.cpp (included there, ONE translation unit, behind hmx_api_graph.inc, whose graph_outputs it shares, and
-// hmx_api_metrics.inc, whose knn_device it runs): hmx_snn_from_knn and hmx_snn_graph (include/harmony_mi355x_snn.h; DESIGN "Seurat's SNN graph").
-// Kernels: hmx_graph.hip.  The calls keep no state on the handle but the timers and the counters of the last call.
+// hmx_api_snn.inc -- part of hmx_api.cpp (included there, ONE translation unit): hmx_snn_from_knn and hmx_snn_graph
+// (include/harmony_mi355x_snn.h; DESIGN "Seurat's SNN graph").  Kernels: hmx_graph.hip.  The search, the check of the lists, the transposed
+// lists and the CSR emit are the call seam's (hmx_api_call.inc).  The calls keep no state on the handle but the timers and the counters of
+// the last call.
 
 namespace {
 
@@ -21,7 +22,6 @@ std::vector<float> snn_weights(int k) {
 int snn_device(hmx_ctx* ctx, CallBufs& B, const int* didx, int64_t N, int32_t m, double prune,
                int64_t* indptr, int32_t* indices, float* weights, int64_t capacity) {
   hipStream_t st = ctx->L.stream;
-  const size_t cnt = (size_t)N * m;
   const int k = m + 1;
   const std::vector<float> jtab = snn_weights(k);
   ctx->snn_s_min = snn_s_min(k, prune);
@@ -31,41 +31,29 @@ int snn_device(hmx_ctx* ctx, CallBufs& B, const int* didx, int64_t N, int32_t m,
   SnnDev S{};
   S.idx = didx; S.N = N; S.m = m; S.s_min = (int)ctx->snn_s_min;
   long long* bsum; long long* dindptr; float* djtab;
-  HIPCHK(B.get(&G.deg, (size_t)N)); HIPCHK(B.get(&G.toff, (size_t)N + 1));
-  HIPCHK(B.get(&G.tkey, cnt)); HIPCHK(B.get(&G.tother, cnt));
-  HIPCHK(B.get(&G.longrows, cnt / GR_WAVE_KEYS + 1)); HIPCHK(B.get(&G.nlong, 1));
   HIPCHK(B.get(&S.cand, (size_t)N)); HIPCHK(B.get(&S.longrows, (size_t)N)); HIPCHK(B.get(&S.nlong, 1));
-  HIPCHK(B.get(&S.len, (size_t)N)); HIPCHK(B.get(&dindptr, (size_t)N + 1)); HIPCHK(B.get(&djtab, jtab.size()));
-  HIPCHK(B.get(&bsum, (size_t)(N + GR_SCAN_CHUNK - 1) / GR_SCAN_CHUNK + 1));
-  HIPCHK(hipMemsetAsync(G.deg, 0, (size_t)N * sizeof(unsigned), st));
-  HIPCHK(hipMemsetAsync(G.nlong, 0, sizeof(unsigned), st));
-  HIPCHK(hipMemsetAsync(S.nlong, 0, sizeof(unsigned), st));
-  HIPCHK(hipMemsetAsync(S.len, 0, (size_t)N * sizeof(unsigned), st));
-  HIPCHK(hipMemcpyAsync(djtab, jtab.data(), jtab.size() * sizeof(float), hipMemcpyHostToDevice, st));
+  HIPCHK(B.get(&S.len, (size_t)N));
+  HIPCHK(zero_fill(S.nlong, 1, st));
+  HIPCHK(zero_fill(S.len, (size_t)N, st));
+  HIPCHK(B.put(&djtab, jtab.data(), jtab.size(), st));
+  CHK(transposed_lists(ctx, B, G, &bsum, [&]() -> int { l_snn_indegree(ctx->L, G); KCHK(); return 0; }));
   S.toff = G.toff; S.tkey = G.tkey; S.jtab = djtab;
-  l_snn_indegree(ctx->L, G); KCHK();
-  l_graph_scan(ctx->L, G.deg, N, G.toff, bsum); KCHK();
-  l_graph_place(ctx->L, G); KCHK();
-  l_graph_sort(ctx->L, G); KCHK();
   l_snn_rowweight(ctx->L, S); KCHK();
   l_snn_short(ctx->L, S, false); KCHK();
   l_snn_long(ctx->L, S, false); KCHK();
-  l_graph_scan(ctx->L, S.len, N, dindptr, bsum); KCHK();
+  CHK(csr_offsets(ctx, B, S.len, N, bsum, indptr, &dindptr));
   unsigned nlong = 0;
-  HIPCHK(hipMemcpyAsync(indptr, dindptr, ((size_t)N + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(&nlong, S.nlong, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+  HIPCHK(download(&nlong, S.nlong, 1, st));
   HIPCHK(hipStreamSynchronize(st));
   ctx->snn_long_rows = (int64_t)nlong;
   const int64_t nnz = indptr[N];
-  if (nnz < 0 || (double)nnz > (double)N * (double)N) return fail(ctx, HMX_ERR_DEVICE, "snn: the row lengths do not add up");
-  if (capacity < nnz) return fail(ctx, HMX_ERR_LIMIT, "capacity " + std::to_string(capacity) + " is below the graph's " + std::to_string(nnz) + " entries (indptr is written)");
+  CHK(csr_entries(ctx, B, "snn", nnz, (double)N * (double)N, capacity, &S.indices, &S.weights));
   if (!nnz) return 0;
   S.indptr = dindptr;
-  HIPCHK(B.get(&S.indices, (size_t)nnz)); HIPCHK(B.get(&S.weights, (size_t)nnz));
   l_snn_short(ctx->L, S, true); KCHK();
   l_snn_long(ctx->L, S, true); KCHK();
-  HIPCHK(hipMemcpyAsync(indices, S.indices, (size_t)nnz * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(weights, S.weights, (size_t)nnz * sizeof(float), hipMemcpyDeviceToHost, st));
+  HIPCHK(download(indices, S.indices, (size_t)nnz, st));
+  HIPCHK(download(weights, S.weights, (size_t)nnz, st));
   HIPCHK(hipStreamSynchronize(st));
   return 0;
 }
@@ -86,28 +74,12 @@ int hmx_snn_from_knn(hmx_ctx* ctx, const int32_t* idx, int64_t N, int32_t m, dou
   if (!idx) return fail(ctx, HMX_ERR_ARG, "null neighbour lists");
   CHK(graph_outputs(ctx, indptr, indices, weights, capacity));
   CHK(snn_prune(ctx, prune));
-  if (N <= 0 || m <= 0) return fail(ctx, HMX_ERR_ARG, "non-positive dimension");
-  if (m > 128) return fail(ctx, HMX_ERR_LIMIT, "supported envelope: at most 128 neighbours");
-  if (N > 2000000000ll) return fail(ctx, HMX_ERR_LIMIT, "at most 2e9 rows");
-  std::vector<int32_t> row((size_t)m);
-  for (int64_t i = 0; i < N; i++) {
-    for (int32_t j = 0; j < m; j++) {
-      const int32_t v = idx[(size_t)i * m + j];
-      if (v < -1 || v >= N) return fail(ctx, HMX_ERR_ARG, "neighbour index outside [-1, N) (row " + std::to_string(i) + ")");
-      if (v == i) return fail(ctx, HMX_ERR_ARG, "row " + std::to_string(i) + " lists its own cell: the lists exclude self");
-      row[(size_t)j] = v;
-    }
-    std::sort(row.begin(), row.end());
-    for (int32_t j = 1; j < m; j++)
-      if (row[(size_t)j] >= 0 && row[(size_t)j] == row[(size_t)j - 1]) return fail(ctx, HMX_ERR_ARG, "row " + std::to_string(i) + " lists a cell twice");
-  }
+  CHK(check_lists(ctx, idx, nullptr, true, N, m));
   CHK(call_device(ctx));
   const double t0 = now_ms();
   CallBufs B;
   int* didx;
-  const size_t cnt = (size_t)N * m;
-  HIPCHK(B.get(&didx, cnt));
-  HIPCHK(hipMemcpyAsync(didx, idx, cnt * sizeof(int32_t), hipMemcpyHostToDevice, ctx->L.stream));
+  HIPCHK(B.put(&didx, idx, (size_t)N * m, ctx->L.stream));
   const int s = snn_device(ctx, B, didx, N, m, prune, indptr, indices, weights, capacity);
   ctx->timers["snn"] = now_ms() - t0;
   return s;
@@ -121,27 +93,15 @@ int hmx_snn_graph(hmx_ctx* ctx, const void* X, int32_t x_dtype, int32_t x_locati
   CHK(graph_outputs(ctx, indptr, indices, weights, capacity));
   CHK(snn_prune(ctx, prune));
   CHK(score_limits(ctx, N, d));
-  if (k < 2 || k > SNN_MAX_K) return fail(ctx, HMX_ERR_LIMIT, "supported envelope: 2 <= k <= 129");
-  if (k > N) return fail(ctx, HMX_ERR_LIMIT, "k counts the cell itself: at most N");
+  CHK(check_neighbor_count(ctx, "k", k, N));
   const int m = k - 1;
   CHK(call_device(ctx));
   const double t0 = now_ms();
   CallBufs B;
-  KnnDev P{};
-  P.zs = (d + 3) / 4 * 4; P.k = m; P.excl = 1; P.N = P.Nq = N;
-  float* xr; float* xn;
-  CHK(score_rows(ctx, B, X, x_dtype, x_location, N, d, P.zs, &xr, &xn));
-  P.X = P.Q = xr; P.xn = P.qn = xn;
-  const size_t cnt = (size_t)N * m;
-  HIPCHK(B.get(&P.idx, cnt)); HIPCHK(B.get(&P.dist, cnt));
-  CHK(knn_device(ctx, B, P));
-  if (knn_idx) HIPCHK(hipMemcpyAsync(knn_idx, P.idx, cnt * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->L.stream));
-  if (knn_dist) HIPCHK(hipMemcpyAsync(knn_dist, P.dist, cnt * sizeof(float), hipMemcpyDeviceToHost, ctx->L.stream));
-  HIPCHK(hipStreamSynchronize(ctx->L.stream));
-  const double t1 = now_ms();
-  ctx->timers["knn"] = t1 - t0;
-  const int s = snn_device(ctx, B, P.idx, N, m, prune, indptr, indices, weights, capacity);
-  ctx->timers["snn"] = now_ms() - t1;
+  KnnLists K;
+  CHK(knn_front(ctx, B, t0, X, x_dtype, x_location, N, d, m, knn_idx, knn_dist, K));
+  const int s = snn_device(ctx, B, K.idx, N, m, prune, indptr, indices, weights, capacity);
+  ctx->timers["snn"] = now_ms() - K.t1;
   return s;
 }
 

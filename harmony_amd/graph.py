@@ -19,13 +19,13 @@ _ip = C.POINTER(C.c_int32)
 _lp = C.POINTER(C.c_int64)
 
 
-def _n_neighbors(n_neighbors, N):
-    """scanpy's n_neighbors counts the cell itself: m = n_neighbors - 1 neighbours with self excluded"""
-    n = int(n_neighbors)
-    if n != n_neighbors or n < 2 or n > MAX_K + 1:
-        raise ValueError("n_neighbors must be an integer in 2 .. %d (it counts the cell itself)" % (MAX_K + 1))
+def _neighbor_count(value, N, name):
+    """scanpy's n_neighbors and Seurat's k.param (`name` says which) count the cell itself: m = value - 1 neighbours with self excluded"""
+    n = int(value) if np.isfinite(value) else 0
+    if n != value or n < 2 or n > MAX_K + 1:
+        raise ValueError("%s must be an integer in 2 .. %d (it counts the cell itself)" % (name, MAX_K + 1))
     if n > N:
-        raise ValueError("n_neighbors = %d exceeds the %d cells" % (n, N))
+        raise ValueError("%s = %d exceeds the %d cells" % (name, n, N))
     return n - 1
 
 
@@ -74,7 +74,7 @@ def neighbors(X, n_neighbors=15, device=None, prune_zeros=True):
     neighbour lists alone.  Two calls give identical results."""
     X, xdt = _rows(X, "X")
     N, d = X.shape
-    m = _n_neighbors(n_neighbors, N)
+    m = _neighbor_count(n_neighbors, N, "n_neighbors")
     with _Handle(device) as h:
         out = _neighbor_graph(h.lib, h.h, h.check, X, xdt, N, d, m)
     return _scanpy_pair(out, N, m, prune_zeros)
@@ -83,14 +83,15 @@ def neighbors(X, n_neighbors=15, device=None, prune_zeros=True):
 def harmony_neighbors(obj, n_neighbors=15, prune_zeros=True):
     """Harmony.neighbors: the graph of the handle's current Z_corr (a fitted handle or a mapped query), read where it lives in HBM"""
     N = int(obj._scalar("N_local"))
-    m = _n_neighbors(n_neighbors, N)
+    m = _neighbor_count(n_neighbors, N, "n_neighbors")
     return _scanpy_pair(_neighbor_graph(obj._lib, obj._h, obj._check, None, 0, N, 0, m), N, m, prune_zeros)
 
 
-def _check_lists(idx, dist):
-    idx, dist = np.asarray(idx), np.asarray(dist)
-    if idx.ndim != 2 or idx.shape != dist.shape or idx.shape[0] < 1 or idx.shape[1] < 1:
-        raise ValueError("idx and dist must be N x m matrices of one shape")
+def _check_lists(idx, dist=None, no_duplicates=False):
+    """neighbour lists idx (N x m, self excluded, -1: an unfilled slot), with their distances or without -> (int32 idx, float32 dist or None)"""
+    idx, dist = np.asarray(idx), None if dist is None else np.asarray(dist)
+    if idx.ndim != 2 or idx.shape[0] < 1 or idx.shape[1] < 1 or (dist is not None and dist.shape != idx.shape):
+        raise ValueError("idx must be an N x m matrix" if dist is None else "idx and dist must be N x m matrices of one shape")
     N, m = idx.shape
     if m > MAX_K:
         raise ValueError("at most %d neighbours per cell" % MAX_K)
@@ -98,9 +99,13 @@ def _check_lists(idx, dist):
         raise ValueError("neighbour indices must be integers in [-1, %d) (-1: an unfilled slot)" % N)
     if np.any(idx == np.arange(N)[:, None]):
         raise ValueError("a row lists its own cell: the neighbour lists exclude self")
-    if np.any(np.isnan(dist) & (idx >= 0)):
+    if dist is not None and np.any(np.isnan(dist) & (idx >= 0)):
         raise ValueError("NaN distances")
-    return np.ascontiguousarray(idx, dtype=np.int32), np.ascontiguousarray(dist, dtype=np.float32)
+    if no_duplicates:
+        srt = np.sort(idx, axis=1)
+        if np.any((srt[:, 1:] == srt[:, :-1]) & (srt[:, 1:] >= 0)):
+            raise ValueError("a row lists a cell twice")
+    return np.ascontiguousarray(idx, dtype=np.int32), None if dist is None else np.ascontiguousarray(dist, dtype=np.float32)
 
 
 def graph_from_knn(idx, dist, device=None, prune_zeros=True, return_scales=False):

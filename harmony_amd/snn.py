@@ -10,24 +10,9 @@ import ctypes as C
 import numpy as np
 
 from ._call import _Handle, _rows
-from .graph import _csr
-from .metrics import MAX_K
-
-_fp = C.POINTER(C.c_float)
-_ip = C.POINTER(C.c_int32)
-_lp = C.POINTER(C.c_int64)
+from .graph import _check_lists, _csr, _fp, _ip, _lp, _neighbor_count
 
 HMX_ERR_LIMIT = 7
-
-
-def _k(k, N):
-    """Seurat's k.param counts the cell itself: m = k - 1 neighbours with self excluded"""
-    n = int(k) if np.isfinite(k) else 0
-    if n != k or n < 2 or n > MAX_K + 1:
-        raise ValueError("k must be an integer in 2 .. %d (it counts the cell itself)" % (MAX_K + 1))
-    if n > N:
-        raise ValueError("k = %d exceeds the %d cells" % (n, N))
-    return n - 1
 
 
 def _prune(prune):
@@ -35,23 +20,6 @@ def _prune(prune):
     if not 0.0 <= p <= 1.0:                                # (NaN fails both comparisons)
         raise ValueError("prune must lie in [0, 1]")
     return p
-
-
-def _check_lists(idx):
-    idx = np.asarray(idx)
-    if idx.ndim != 2 or idx.shape[0] < 1 or idx.shape[1] < 1:
-        raise ValueError("idx must be an N x m matrix")
-    N, m = idx.shape
-    if m > MAX_K:
-        raise ValueError("at most %d neighbours per cell" % MAX_K)
-    if not np.issubdtype(idx.dtype, np.integer) or np.any(idx < -1) or np.any(idx >= N):
-        raise ValueError("neighbour indices must be integers in [-1, %d) (-1: an unfilled slot)" % N)
-    if np.any(idx == np.arange(N)[:, None]):
-        raise ValueError("a row lists its own cell: the neighbour lists exclude self")
-    srt = np.sort(idx, axis=1)
-    if np.any((srt[:, 1:] == srt[:, :-1]) & (srt[:, 1:] >= 0)):
-        raise ValueError("a row lists a cell twice")
-    return np.ascontiguousarray(idx, dtype=np.int32)
 
 
 def _snn_call(lib, handle, check, run, N, m):
@@ -101,7 +69,7 @@ def snn(X, k=20, prune=1.0 / 15.0, device=None):
     results."""
     X, xdt = _rows(X, "X")
     N, d = X.shape
-    m = _k(k, N)
+    m = _neighbor_count(k, N, "k")
     prune = _prune(prune)
     with _Handle(device) as h:
         return _snn_graph(h.lib, h.h, h.check, X, xdt, N, d, m, prune)
@@ -110,14 +78,14 @@ def snn(X, k=20, prune=1.0 / 15.0, device=None):
 def harmony_snn(obj, k=20, prune=1.0 / 15.0):
     """Harmony.snn: (nn, snn) of the handle's current Z_corr (a fitted handle or a mapped query), read where it lives in HBM"""
     N = int(obj._scalar("N_local"))
-    m = _k(k, N)
+    m = _neighbor_count(k, N, "k")
     return _snn_graph(obj._lib, obj._h, obj._check, None, 0, N, 0, m, _prune(prune))
 
 
 def snn_from_knn(idx, prune=1.0 / 15.0, device=None):
     """The SNN stage alone: the graph of the neighbour lists idx (N x m, self excluded, as knn(X, m) returns them; idx -1 marks an unfilled
     slot; k = m + 1)."""
-    idx = _check_lists(idx)
+    idx = _check_lists(idx, no_duplicates=True)[0]
     N, m = idx.shape
     prune = _prune(prune)
     with _Handle(device) as h:

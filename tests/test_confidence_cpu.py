@@ -14,6 +14,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import confidence_ref as cr  # noqa: E402
+import helpers  # noqa: E402
 import map_query_ref as mq  # noqa: E402
 import harmony_amd  # noqa: E402
 from harmony_amd import HarmonyReference, _lib, mapping_confidence  # noqa: E402
@@ -167,27 +168,14 @@ def test_python_errors_come_before_the_library(monkeypatch):
 
 
 def test_confidence_header_matches_the_library_and_the_binding():
-    lib = _lib.load()
-    inc = os.path.join(ROOT, "include")
-    names = lambda f: set(re.findall(r"\b(hmx_[a-z0-9_]+)\s*\(", open(os.path.join(inc, f)).read())) - {"hmx_allreduce_fn"}  # noqa: E731
-    conf = names("harmony_mi355x_confidence.h")
-    assert conf == set(_lib.CONFIDENCE_SIGNATURES) == {"hmx_reference_moments", "hmx_mapping_confidence"}
-    for other in ("harmony_mi355x.h", "harmony_mi355x_lab.h", "harmony_mi355x_metrics.h", "harmony_mi355x_silhouette.h"):
-        assert not (conf & names(other)), other
-    assert not (set(_lib.CONFIDENCE_SIGNATURES) & (set(_lib.SIGNATURES) | set(_lib.METRICS_SIGNATURES) | set(_lib.SILHOUETTE_SIGNATURES)))
-    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(inc, "harmony_mi355x_confidence.h")).read(), flags=re.S)
-    ctype = {"hmx_ctx*": C.c_void_p, "int32_t": C.c_int32, "double": C.c_double, "const double*": C.POINTER(C.c_double),
-             "double*": C.POINTER(C.c_double), "float*": C.POINTER(C.c_float)}
-    found = re.findall(r"int (hmx_[a-z_]+)\(([^)]*)\)", hdr)
-    assert [n for n, _ in found] == ["hmx_reference_moments", "hmx_mapping_confidence"]
-    for n, args in found:
-        fn = getattr(lib, n)
-        sig = _lib.CONFIDENCE_SIGNATURES[n][1]
-        assert fn.restype is C.c_int and list(fn.argtypes) == sig
-        types = [" ".join(a.split()[:-1]) for a in args.replace("\n", " ").split(",")]
-        assert len(types) == len(sig), n
-        for t, s in zip(types, sig):
-            assert s is ctype[t] or s == ctype[t], (n, t, s)
+    mine = ["hmx_reference_moments", "hmx_mapping_confidence"]
+    assert helpers.header_names("harmony_mi355x_confidence.h") == set(_lib.CONFIDENCE_SIGNATURES) == set(mine)
+    found = helpers.header_functions("harmony_mi355x_confidence.h")
+    assert [n for n, _ in found] == mine
+    helpers.assert_header_stands_alone("harmony_mi355x_confidence.h", mine)
+    for n, types in found:
+        helpers.assert_binding_matches(_lib.load(), n, types, _lib.CONFIDENCE_SIGNATURES[n][1])
+    hdr = helpers.header_text("harmony_mi355x_confidence.h")
     assert re.search(r"#define HMX_SPACE_ORIG 0\b", hdr) and re.search(r"#define HMX_SPACE_CORR 1\b", hdr)
     assert harmony_amd.mapping.SPACES == ("orig", "corr")
 

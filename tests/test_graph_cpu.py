@@ -3,7 +3,6 @@ independent arithmetic (scipy's fuzzy union of the directed membership matrix, t
 scipy's connected components); the argument errors need no device (tests/test_gpu_graph.py runs the library)."""
 import ctypes as C
 import os
-import re
 import sys
 
 import numpy as np
@@ -14,41 +13,21 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import graph_ref as gr  # noqa: E402
+import helpers  # noqa: E402
 import metrics_ref as mr  # noqa: E402
 from harmony_amd import Harmony, _lib, connected_components, graph_connectivity, graph_from_knn, neighbors  # noqa: E402
 
 sp = pytest.importorskip("scipy.sparse")
 csgraph = pytest.importorskip("scipy.sparse.csgraph")
 
-OTHER_HEADERS = ("harmony_mi355x.h", "harmony_mi355x_lab.h", "harmony_mi355x_metrics.h", "harmony_mi355x_silhouette.h", "harmony_mi355x_confidence.h",
-                 "harmony_mi355x_project.h", "harmony_mi355x_pca.h", "harmony_mi355x_groups.h", "harmony_mi355x_ranksum.h")
-OTHER_TABLES = ("SIGNATURES", "METRICS_SIGNATURES", "SILHOUETTE_SIGNATURES", "CONFIDENCE_SIGNATURES", "PROJECT_SIGNATURES", "PCA_SIGNATURES",
-                "GROUPS_SIGNATURES", "RANKSUM_SIGNATURES")
-
 
 def test_graph_header_matches_the_library_and_the_binding():
-    lib = _lib.load()
-    inc = os.path.join(ROOT, "include")
-    names = lambda f: set(re.findall(r"\b(hmx_[a-z0-9_]+)\s*\(", open(os.path.join(inc, f)).read())) - {"hmx_allreduce_fn"}  # noqa: E731
-    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(inc, "harmony_mi355x_graph.h")).read(), flags=re.S)
-    found = re.findall(r"int (hmx_[a-z_]+)\(([^)]*)\)", hdr)
+    found = helpers.header_functions("harmony_mi355x_graph.h")
     mine = [n for n, _ in found]
     assert mine == ["hmx_graph_from_knn", "hmx_neighbor_graph", "hmx_graph_components"] and set(mine) == set(_lib.GRAPH_SIGNATURES)
-    for other in OTHER_HEADERS:
-        assert not (set(mine) & names(other)), other
-    for table in OTHER_TABLES:
-        assert not (set(mine) & set(getattr(_lib, table))), table
-    ctype = {"hmx_ctx*": (C.c_void_p,), "int32_t": (C.c_int32,), "int64_t": (C.c_int64,), "const void*": (C.c_void_p,),
-             "const int32_t*": (C.POINTER(C.c_int32),), "int32_t*": (C.POINTER(C.c_int32),), "const float*": (C.POINTER(C.c_float),),
-             "float*": (C.POINTER(C.c_float),), "const int64_t*": (C.POINTER(C.c_int64),), "int64_t*": (C.POINTER(C.c_int64),),
-             "double*": (C.POINTER(C.c_double),)}
-    for name, arglist in found:
-        fn, sig = getattr(lib, name), _lib.GRAPH_SIGNATURES[name][1]
-        assert fn.restype is C.c_int and list(fn.argtypes) == sig
-        types = [" ".join(a.split()[:-1]) for a in arglist.replace("\n", " ").split(",")]
-        assert len(types) == len(sig), name
-        for t, s in zip(types, sig):
-            assert any(s is o or s == o for o in ctype[t]), (name, t, s)
+    helpers.assert_header_stands_alone("harmony_mi355x_graph.h", mine)
+    for name, types in found:
+        helpers.assert_binding_matches(_lib.load(), name, types, _lib.GRAPH_SIGNATURES[name][1])
 
 
 # ---- the spec against independent arithmetic -------------------------------------------------------------------------------------------------

@@ -5,7 +5,6 @@ tests/cpp/group_plan_probe.cpp) covers every kept cell exactly once; the argumen
 import ctypes as C
 import functools
 import os
-import re
 import subprocess
 import sys
 import tempfile
@@ -18,37 +17,21 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import group_stats_ref as gr  # noqa: E402
+import helpers  # noqa: E402
 from harmony_amd import _lib  # noqa: E402
 from harmony_amd import gene_stats_by_group, markers_from_sums, rank_genes_groups, variable_genes  # noqa: E402
 from harmony_amd.group_stats import select_variable_genes  # noqa: E402
 
 
 def test_groups_header_matches_the_library_and_the_binding():
-    lib = _lib.load()
-    inc = os.path.join(ROOT, "include")
-    names = lambda f: set(re.findall(r"\b(hmx_[a-z0-9_]+)\s*\(", open(os.path.join(inc, f)).read())) - {"hmx_allreduce_fn"}  # noqa: E731
-    grp = names("harmony_mi355x_groups.h")
-    assert grp == set(_lib.GROUPS_SIGNATURES) == {"hmx_gene_stats_grouped"}
-    for other in ("harmony_mi355x.h", "harmony_mi355x_lab.h", "harmony_mi355x_metrics.h", "harmony_mi355x_silhouette.h", "harmony_mi355x_confidence.h",
-                  "harmony_mi355x_project.h", "harmony_mi355x_pca.h"):
-        assert not (grp & names(other)), other
-    assert not (set(_lib.GROUPS_SIGNATURES) & (set(_lib.SIGNATURES) | set(_lib.METRICS_SIGNATURES) | set(_lib.SILHOUETTE_SIGNATURES)
-                                               | set(_lib.CONFIDENCE_SIGNATURES) | set(_lib.PROJECT_SIGNATURES) | set(_lib.PCA_SIGNATURES)))
-    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(inc, "harmony_mi355x_groups.h")).read(), flags=re.S)
-    ctype = {"hmx_ctx*": (C.c_void_p,), "int32_t": (C.c_int32,), "int64_t": (C.c_int64,), "double": (C.c_double,),
-             "const double*": (C.POINTER(C.c_double),), "double*": (C.POINTER(C.c_double),), "int64_t*": (C.POINTER(C.c_int64),),
-             "const int32_t*": (C.POINTER(C.c_int32), C.c_void_p), "const int64_t*": (C.c_void_p,), "const void*": (C.c_void_p,)}
-    found = re.findall(r"int (hmx_[a-z_]+)\(([^)]*)\)", hdr)
-    assert [n for n, _ in found] == ["hmx_gene_stats_grouped"]
-    fn, sig = lib.hmx_gene_stats_grouped, _lib.GROUPS_SIGNATURES["hmx_gene_stats_grouped"][1]
-    assert fn.restype is C.c_int and list(fn.argtypes) == sig
-    types = [" ".join(a.split()[:-1]) for a in found[0][1].replace("\n", " ").split(",")]
-    assert len(types) == len(sig) == 17
-    for t, s in zip(types, sig):
-        assert any(s is o or s == o for o in ctype[t]), (t, s)
+    assert helpers.header_names("harmony_mi355x_groups.h") == set(_lib.GROUPS_SIGNATURES) == {"hmx_gene_stats_grouped"}
+    found = helpers.header_functions("harmony_mi355x_groups.h")
+    assert [n for n, _ in found] == ["hmx_gene_stats_grouped"] and len(found[0][1]) == 17
+    helpers.assert_header_stands_alone("harmony_mi355x_groups.h", ["hmx_gene_stats_grouped"])
+    loose = {"const int32_t*": (C.POINTER(C.c_int32), C.c_void_p), "const int64_t*": (C.c_void_p,)}      # (the count matrix: host or device pointers)
+    helpers.assert_binding_matches(_lib.load(), "hmx_gene_stats_grouped", found[0][1], _lib.GROUPS_SIGNATURES["hmx_gene_stats_grouped"][1], loose)
 
 
-# ---- the bars ------------------------------------------------------------------------------------------------------------------------------------
 def A(c):
     return c["data"], c["indices"], c["indptr"], c["G_all"]
 

@@ -3,7 +3,6 @@ include/harmony_mi355x_metrics.h against the library and harmony_amd/_lib.py, th
 the library is loaded) and of the library (before the device is touched), and the refusal to run without a device."""
 import ctypes as C
 import os
-import re
 import sys
 
 import numpy as np
@@ -13,6 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
+import helpers  # noqa: E402
 import metrics_ref as mr  # noqa: E402
 import harmony_amd  # noqa: E402
 from harmony_amd import _lib, metrics  # noqa: E402
@@ -55,27 +55,14 @@ def test_spec_knn_ties_duplicates_and_self_exclusion():
 
 
 def test_metrics_header_matches_the_library_and_the_binding():
-    lib = _lib.load()
-    inc = os.path.join(ROOT, "include")
-    names = lambda f: set(re.findall(r"\b(hmx_[a-z0-9_]+)\s*\(", open(os.path.join(inc, f)).read())) - {"hmx_allreduce_fn"}  # noqa: E731
-    met = names("harmony_mi355x_metrics.h")
+    met = helpers.header_names("harmony_mi355x_metrics.h")
     assert met == set(_lib.METRICS_SIGNATURES) and len(met) == 3
-    assert not (met & names("harmony_mi355x.h")) and not (met & names("harmony_mi355x_lab.h"))
-    assert not (set(_lib.METRICS_SIGNATURES) & set(_lib.SIGNATURES))
-    for n in met:
-        fn = getattr(lib, n)
-        assert fn.restype is C.c_int and list(fn.argtypes) == _lib.METRICS_SIGNATURES[n][1]
-    # the argument lists of the header, type by type
-    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(inc, "harmony_mi355x_metrics.h")).read(), flags=re.S)
-    ctype = {"hmx_ctx*": C.c_void_p, "const void*": C.c_void_p, "int32_t": C.c_int32, "int64_t": C.c_int64, "double": C.c_double,
-             "const int32_t*": C.POINTER(C.c_int32), "const float*": C.POINTER(C.c_float), "double*": C.POINTER(C.c_double)}
-    outputs = {"int32_t*": (C.c_void_p, C.POINTER(C.c_int32)), "float*": (C.c_void_p, C.POINTER(C.c_float))}      # (host or device pointers)
-    for n, args in re.findall(r"int (hmx_[a-z_]+)\(([^)]*)\)", hdr):
-        types = [" ".join(a.split()[:-1]) for a in args.replace("\n", " ").split(",")]
-        sig = _lib.METRICS_SIGNATURES[n][1]
-        assert len(types) == len(sig), n
-        for t, s in zip(types, sig):
-            assert s in outputs[t] if t in outputs else s is ctype[t] or s == ctype[t], (n, t, s)
+    found = helpers.header_functions("harmony_mi355x_metrics.h")
+    assert {n for n, _ in found} == met
+    helpers.assert_header_stands_alone("harmony_mi355x_metrics.h", met)
+    loose = {"int32_t*": (C.c_void_p, C.POINTER(C.c_int32)), "float*": (C.c_void_p, C.POINTER(C.c_float))}      # (the outputs: host or device pointers)
+    for n, types in found:
+        helpers.assert_binding_matches(_lib.load(), n, types, _lib.METRICS_SIGNATURES[n][1], loose)
     assert {"knn", "compute_lisi", "lisi_from_knn", "knn_predict"} <= set(harmony_amd.__all__) and hasattr(harmony_amd.Harmony, "lisi")
 
 

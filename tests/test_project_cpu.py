@@ -14,6 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
+import helpers  # noqa: E402
 import project_ref as pr  # noqa: E402
 import harmony_amd  # noqa: E402
 from harmony_amd import HarmonyError, HarmonyLoadings, _lib, project, project_query  # noqa: E402
@@ -220,28 +221,12 @@ def test_module_imports_without_scipy():
 
 
 def test_project_header_matches_the_library_and_the_binding():
-    lib = _lib.load()
-    inc = os.path.join(ROOT, "include")
-    names = lambda f: set(re.findall(r"\b(hmx_[a-z0-9_]+)\s*\(", open(os.path.join(inc, f)).read())) - {"hmx_allreduce_fn"}  # noqa: E731
-    proj = names("harmony_mi355x_project.h")
-    assert proj == set(_lib.PROJECT_SIGNATURES) == {"hmx_project_counts"}
-    for other in ("harmony_mi355x.h", "harmony_mi355x_lab.h", "harmony_mi355x_metrics.h", "harmony_mi355x_silhouette.h", "harmony_mi355x_confidence.h"):
-        assert not (proj & names(other)), other
-    assert not (set(_lib.PROJECT_SIGNATURES) & (set(_lib.SIGNATURES) | set(_lib.METRICS_SIGNATURES) | set(_lib.SILHOUETTE_SIGNATURES)
-                                                | set(_lib.CONFIDENCE_SIGNATURES)))
-    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(inc, "harmony_mi355x_project.h")).read(), flags=re.S)
-    ctype = {"hmx_ctx*": C.c_void_p, "int32_t": C.c_int32, "int64_t": C.c_int64, "double": C.c_double, "const double*": C.POINTER(C.c_double),
-             "const int32_t*": (C.POINTER(C.c_int32), C.c_void_p), "const int64_t*": (C.c_void_p,), "const void*": (C.c_void_p,), "void*": (C.c_void_p,)}
-    found = re.findall(r"int (hmx_[a-z_]+)\(([^)]*)\)", hdr)
-    assert [n for n, _ in found] == ["hmx_project_counts"]
-    fn = lib.hmx_project_counts
-    sig = _lib.PROJECT_SIGNATURES["hmx_project_counts"][1]
-    assert fn.restype is C.c_int and list(fn.argtypes) == sig
-    types = [" ".join(a.split()[:-1]) for a in found[0][1].replace("\n", " ").split(",")]
-    assert len(types) == len(sig) == 19
-    for t, s in zip(types, sig):
-        ok = ctype[t] if isinstance(ctype[t], tuple) else (ctype[t],)
-        assert any(s is o or s == o for o in ok), (t, s)
+    assert helpers.header_names("harmony_mi355x_project.h") == set(_lib.PROJECT_SIGNATURES) == {"hmx_project_counts"}
+    found = helpers.header_functions("harmony_mi355x_project.h")
+    assert [n for n, _ in found] == ["hmx_project_counts"] and len(found[0][1]) == 19
+    helpers.assert_header_stands_alone("harmony_mi355x_project.h", ["hmx_project_counts"])
+    loose = {"const int32_t*": (C.POINTER(C.c_int32), C.c_void_p), "const int64_t*": (C.c_void_p,)}      # (the count matrix: host or device pointers)
+    helpers.assert_binding_matches(_lib.load(), "hmx_project_counts", found[0][1], _lib.PROJECT_SIGNATURES["hmx_project_counts"][1], loose)
 
 
 def _call_factory(lib, h):

@@ -18,40 +18,22 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
+import helpers  # noqa: E402
 import rank_sums_ref as rr  # noqa: E402
 from harmony_amd import _lib  # noqa: E402
 from harmony_amd import rank_genes_groups, rank_sums_by_group, wilcoxon_from_rank_sums  # noqa: E402
 
-OTHER_HEADERS = ("harmony_mi355x.h", "harmony_mi355x_lab.h", "harmony_mi355x_metrics.h", "harmony_mi355x_silhouette.h", "harmony_mi355x_confidence.h",
-                 "harmony_mi355x_project.h", "harmony_mi355x_pca.h", "harmony_mi355x_groups.h")
-OTHER_TABLES = ("SIGNATURES", "METRICS_SIGNATURES", "SILHOUETTE_SIGNATURES", "CONFIDENCE_SIGNATURES", "PROJECT_SIGNATURES", "PCA_SIGNATURES", "GROUPS_SIGNATURES")
-
-
 def test_ranksum_header_matches_the_library_and_the_binding():
-    lib = _lib.load()
-    inc = os.path.join(ROOT, "include")
-    names = lambda f: set(re.findall(r"\b(hmx_[a-z0-9_]+)\s*\(", open(os.path.join(inc, f)).read())) - {"hmx_allreduce_fn"}  # noqa: E731
-    rs = names("harmony_mi355x_ranksum.h")
-    assert rs == set(_lib.RANKSUM_SIGNATURES) == {"hmx_rank_sums"}
-    for other in OTHER_HEADERS:
-        assert not (rs & names(other)), other
-    for table in OTHER_TABLES:
-        assert not (set(_lib.RANKSUM_SIGNATURES) & set(getattr(_lib, table))), table
-    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(inc, "harmony_mi355x_ranksum.h")).read(), flags=re.S)
-    ctype = {"hmx_ctx*": (C.c_void_p,), "int32_t": (C.c_int32,), "int64_t": (C.c_int64,), "double": (C.c_double,),
-             "const double*": (C.POINTER(C.c_double),), "int64_t*": (C.POINTER(C.c_int64),), "uint64_t*": (C.POINTER(C.c_uint64),),
-             "const int32_t*": (C.POINTER(C.c_int32), C.c_void_p), "const int64_t*": (C.c_void_p,), "const void*": (C.c_void_p,)}
-    found = re.findall(r"int (hmx_[a-z_]+)\(([^)]*)\)", hdr)
-    assert [n for n, _ in found] == ["hmx_rank_sums"]
-    fn, sig = lib.hmx_rank_sums, _lib.RANKSUM_SIGNATURES["hmx_rank_sums"][1]
-    assert fn.restype is C.c_int and list(fn.argtypes) == sig
-    args = [a.split() for a in found[0][1].replace("\n", " ").split(",")]
-    types = [" ".join(a[:-1]) for a in args]
-    assert len(types) == len(sig) == 18
-    for t, s in zip(types, sig):
-        assert any(s is o or s == o for o in ctype[t]), (t, s)
+    assert helpers.header_names("harmony_mi355x_ranksum.h") == set(_lib.RANKSUM_SIGNATURES) == {"hmx_rank_sums"}
+    found = helpers.header_functions("harmony_mi355x_ranksum.h")
+    assert [n for n, _ in found] == ["hmx_rank_sums"] and len(found[0][1]) == 18
+    helpers.assert_header_stands_alone("harmony_mi355x_ranksum.h", ["hmx_rank_sums"])
+    loose = {"const int32_t*": (C.POINTER(C.c_int32), C.c_void_p), "const int64_t*": (C.c_void_p,)}      # (the count matrix: host or device pointers)
+    helpers.assert_binding_matches(_lib.load(), "hmx_rank_sums", found[0][1], _lib.RANKSUM_SIGNATURES["hmx_rank_sums"][1], loose)
+    mine = re.findall(r"int hmx_rank_sums\(([^)]*)\)", helpers.header_text("harmony_mi355x_ranksum.h"))[0]
+    args = [a.split() for a in mine.replace("\n", " ").split(",")]
     # hmx_gene_stats_grouped's arguments up to `labels, B`, then gene_slot, G and the four outputs
-    grouped = re.sub(r"/\*.*?\*/", "", open(os.path.join(inc, "harmony_mi355x_groups.h")).read(), flags=re.S)
+    grouped = helpers.header_text("harmony_mi355x_groups.h")
     gargs = [a.split() for a in re.findall(r"int hmx_gene_stats_grouped\(([^)]*)\)", grouped)[0].replace("\n", " ").split(",")]
     assert args[:12] == gargs[:12] and [a[-1] for a in args[12:]] == ["gene_slot", "G", "n_obs", "n_pos", "rank2", "tie3"]
 

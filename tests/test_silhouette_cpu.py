@@ -3,7 +3,6 @@ include/harmony_mi355x_silhouette.h against the library and harmony_amd/_lib.py,
 before the library is loaded) and of the library (before the device is touched), and the refusal to run without a device."""
 import ctypes as C
 import os
-import re
 import sys
 
 import numpy as np
@@ -13,6 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
+import helpers  # noqa: E402
 import silhouette_ref as sr  # noqa: E402
 import harmony_amd  # noqa: E402
 from harmony_amd import _lib, silhouette  # noqa: E402
@@ -105,29 +105,11 @@ def test_scib_aggregates_on_a_hand_made_case():
 
 
 def test_silhouette_header_matches_the_library_and_the_binding():
-    lib = _lib.load()
-    inc = os.path.join(ROOT, "include")
-    names = lambda f: set(re.findall(r"\b(hmx_[a-z0-9_]+)\s*\(", open(os.path.join(inc, f)).read())) - {"hmx_allreduce_fn"}  # noqa: E731
-    sil = names("harmony_mi355x_silhouette.h")
-    assert sil == set(_lib.SILHOUETTE_SIGNATURES) == {"hmx_silhouette"}
-    for other in ("harmony_mi355x.h", "harmony_mi355x_lab.h", "harmony_mi355x_metrics.h"):
-        assert not (sil & names(other)), other
-    assert not (set(_lib.SILHOUETTE_SIGNATURES) & (set(_lib.SIGNATURES) | set(_lib.METRICS_SIGNATURES)))
-    for n in sil:
-        fn = getattr(lib, n)
-        assert fn.restype is C.c_int and list(fn.argtypes) == _lib.SILHOUETTE_SIGNATURES[n][1]
-    # the argument list of the header, type by type
-    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(inc, "harmony_mi355x_silhouette.h")).read(), flags=re.S)
-    ctype = {"hmx_ctx*": C.c_void_p, "const void*": C.c_void_p, "int32_t": C.c_int32, "int64_t": C.c_int64,
-             "const int32_t*": C.POINTER(C.c_int32), "double*": C.POINTER(C.c_double)}
-    found = re.findall(r"int (hmx_[a-z_]+)\(([^)]*)\)", hdr)
-    assert [n for n, _ in found] == ["hmx_silhouette"]
-    for n, args in found:
-        types = [" ".join(a.split()[:-1]) for a in args.replace("\n", " ").split(",")]
-        sig = _lib.SILHOUETTE_SIGNATURES[n][1]
-        assert len(types) == len(sig) == 13, n
-        for t, s in zip(types, sig):
-            assert s is ctype[t] or s == ctype[t], (n, t, s)
+    assert helpers.header_names("harmony_mi355x_silhouette.h") == set(_lib.SILHOUETTE_SIGNATURES) == {"hmx_silhouette"}
+    found = helpers.header_functions("harmony_mi355x_silhouette.h")
+    assert [n for n, _ in found] == ["hmx_silhouette"] and len(found[0][1]) == 13
+    helpers.assert_header_stands_alone("harmony_mi355x_silhouette.h", ["hmx_silhouette"])
+    helpers.assert_binding_matches(_lib.load(), "hmx_silhouette", found[0][1], _lib.SILHOUETTE_SIGNATURES["hmx_silhouette"][1])
     assert {"silhouette_samples", "silhouette_label", "silhouette_batch"} <= set(harmony_amd.__all__) and hasattr(harmony_amd.Harmony, "silhouette")
 
 

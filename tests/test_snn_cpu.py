@@ -3,7 +3,6 @@ set intersections computed row by row and a hand-computed example; the pruning t
 (tests/test_gpu_snn.py runs the library)."""
 import ctypes as C
 import os
-import re
 import sys
 
 import numpy as np
@@ -15,37 +14,19 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 pytest.importorskip("scipy.sparse")
 
+import helpers  # noqa: E402
 import metrics_ref as mr  # noqa: E402
 import snn_ref as sr  # noqa: E402
-from harmony_amd import Harmony, _lib, snn, snn_from_knn  # noqa: E402
-
-OTHER_HEADERS = ("harmony_mi355x.h", "harmony_mi355x_lab.h", "harmony_mi355x_metrics.h", "harmony_mi355x_silhouette.h", "harmony_mi355x_confidence.h",
-                 "harmony_mi355x_project.h", "harmony_mi355x_pca.h", "harmony_mi355x_groups.h", "harmony_mi355x_ranksum.h", "harmony_mi355x_graph.h")
-OTHER_TABLES = ("SIGNATURES", "METRICS_SIGNATURES", "SILHOUETTE_SIGNATURES", "CONFIDENCE_SIGNATURES", "PROJECT_SIGNATURES", "PCA_SIGNATURES",
-                "GROUPS_SIGNATURES", "RANKSUM_SIGNATURES", "GRAPH_SIGNATURES")
+from harmony_amd import Harmony, _lib, neighbors, snn, snn_from_knn  # noqa: E402
 
 
 def test_snn_header_matches_the_library_and_the_binding():
-    lib = _lib.load()
-    inc = os.path.join(ROOT, "include")
-    names = lambda f: set(re.findall(r"\b(hmx_[a-z0-9_]+)\s*\(", open(os.path.join(inc, f)).read())) - {"hmx_allreduce_fn"}  # noqa: E731
-    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(inc, "harmony_mi355x_snn.h")).read(), flags=re.S)
-    found = re.findall(r"int (hmx_[a-z_]+)\(([^)]*)\)", hdr)
+    found = helpers.header_functions("harmony_mi355x_snn.h")
     mine = [n for n, _ in found]
     assert mine == ["hmx_snn_from_knn", "hmx_snn_graph"] and set(mine) == set(_lib.SNN_SIGNATURES)
-    for other in OTHER_HEADERS:
-        assert not (set(mine) & names(other)), other
-    for table in OTHER_TABLES:
-        assert not (set(mine) & set(getattr(_lib, table))), table
-    ctype = {"hmx_ctx*": C.c_void_p, "int32_t": C.c_int32, "int64_t": C.c_int64, "double": C.c_double, "const void*": C.c_void_p,
-             "const int32_t*": C.POINTER(C.c_int32), "int32_t*": C.POINTER(C.c_int32), "float*": C.POINTER(C.c_float), "int64_t*": C.POINTER(C.c_int64)}
-    for name, arglist in found:
-        fn, sig = getattr(lib, name), _lib.SNN_SIGNATURES[name][1]
-        assert fn.restype is C.c_int and list(fn.argtypes) == sig
-        types = [" ".join(a.split()[:-1]) for a in arglist.replace("\n", " ").split(",")]
-        assert len(types) == len(sig), name
-        for t, s in zip(types, sig):
-            assert s is ctype[t] or s == ctype[t], (name, t, s)
+    helpers.assert_header_stands_alone("harmony_mi355x_snn.h", mine)
+    for name, types in found:
+        helpers.assert_binding_matches(_lib.load(), name, types, _lib.SNN_SIGNATURES[name][1])
 
 
 # ---- the spec against independent arithmetic -------------------------------------------------------------------------------------------------
@@ -169,5 +150,39 @@ def test_library_argument_errors_come_before_the_device():
             assert lib.hmx_get(h, key, out1, 1) == 1, key
         assert lib.hmx_get(h, b"snn:short_cap", out1, 1) == 1 and out1[0] >= 129 * 2      # a row whose neighbours nobody else lists is short
         assert lib.hmx_get(h, b"snn:window", out1, 1) == 1 and out1[0] >= 256 and out1[0] % 4 == 0
+    finally:
+        lib.hmx_destroy(h)
+
+
+def test_graph_and_snn_calls_refuse_alike():
+    """the neighbour graph and the SNN graph share the check of neighbour lists and the envelope of the neighbour count: the same bad input is
+    refused with the same status and the same text, up to the parameter's name"""
+    for call, name in ((lambda v: neighbors(np.zeros((10, 4)), n_neighbors=v), "n_neighbors"), (lambda v: snn(np.zeros((10, 4)), k=v), "k")):
+        for bad in (float("nan"), float("inf"), 1, 130, 11):
+            with pytest.raises(ValueError, match=name + " "):
+                call(bad)
+    lib = _lib.load()
+    ip, fp, lp = C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_int64)
+    h = C.c_void_p(lib.hmx_create())
+    ARG, LIMIT = 1, 7
+    try:
+        def both_from_knn(idx, N, m):
+            idx, dist = np.ascontiguousarray(idx, dtype=np.int32), np.ones((N, m), dtype=np.float32)
+            indptr, indices, weights = np.zeros(N + 1, dtype=np.int64), np.zeros(8, dtype=np.int32), np.zeros(8, dtype=np.float32)
+            out = indptr.ctypes.data_as(lp), indices.ctypes.data_as(ip), weights.ctypes.data_as(fp), 8
+            g = lib.hmx_graph_from_knn(h, idx.ctypes.data_as(ip), dist.ctypes.data_as(fp), N, m, *out, None, None), lib.hmx_last_error(h)
+            s = lib.hmx_snn_from_knn(h, idx.ctypes.data_as(ip), N, m, 0.1, *out), lib.hmx_last_error(h)
+            return g, s
+        for idx, N, m, status, text in ((np.array([[1, 3], [0, 2], [0, 1]]), 3, 2, ARG, b"[-1, N) (row 0)"),
+                                        (np.array([[1, 2], [1, 2], [0, 1]]), 3, 2, ARG, b"row 1 lists its own cell"),
+                                        (np.zeros((1, 129)), 1, 129, LIMIT, b"at most 128 neighbours")):
+            g, s = both_from_knn(idx, N, m)
+            assert g == s and g[0] == status and text in g[1], (g, s)
+        X, indptr = np.zeros((10, 4)), np.zeros(11, dtype=np.int64)
+        for k, text in ((1, b"2 <= k <= 129"), (130, b"2 <= k <= 129"), (11, b"k counts the cell itself: at most N")):
+            g = lib.hmx_neighbor_graph(h, C.c_void_p(X.ctypes.data), 0, 0, 10, 4, k, None, None, indptr.ctypes.data_as(lp), None, None, 0,
+                                       None, None), lib.hmx_last_error(h)
+            s = lib.hmx_snn_graph(h, C.c_void_p(X.ctypes.data), 0, 0, 10, 4, k, 0.1, None, None, indptr.ctypes.data_as(lp), None, None, 0), lib.hmx_last_error(h)
+            assert g[0] == s[0] == LIMIT and text in s[1] and b"n_neighbors" in g[1] and g[1].replace(b"n_neighbors", b"k") == s[1], (g, s)
     finally:
         lib.hmx_destroy(h)

@@ -13,9 +13,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = [os.path.join(HERE, "csrc", f) for f in ("hmx_kernels.hip", "hmx_tile_bf.hip", "hmx_seq.hip", "hmx_query.hip", "hmx_confidence.hip", "hmx_project.hip", "hmx_pca.hip", "hmx_ranksum.hip", "hmx_graph.hip", "hmx_knn.hip", "hmx_silhouette.hip", "hmx_api.cpp")]
 # (hmx_tile_bf.hip is hmx_kernels.hip's tile kernel built a second time with the split-bf16 distance GEMM: it includes that file)
 _INC = [os.path.join(HERE, "csrc", f) for f in ("hmx_k_stream.inc", "hmx_k_tile.inc", "hmx_k_correct.inc", "hmx_k_launch.inc")]      # the kernels, by section (included by hmx_kernels.hip)
-_API_INC = [os.path.join(HERE, "csrc", "hmx_api_%s.inc" % f) for f in ("seam", "kmeans", "refarith", "update", "ridge", "p2p", "setup", "query", "diag", "call", "metrics", "silhouette", "confidence", "csr", "project", "pca", "groups", "ranksum", "graph", "snn")]    # the host orchestration, by section (included by hmx_api.cpp)
+_API_INC = [os.path.join(HERE, "csrc", "hmx_api_%s.inc" % f) for f in ("xfer", "seam", "kmeans", "refarith", "update", "ridge", "p2p", "setup", "query", "diag", "call", "metrics", "silhouette", "confidence", "csr", "project", "pca", "groups", "ranksum", "graph", "snn")]    # the host orchestration, by section (included by hmx_api.cpp)
 _PLAN = [os.path.join(HERE, "csrc", "hmx_plan.h")]      # the launch plan (host code only): of a fit for hmx_setup (hmx_api.cpp), of every k_tile launch for the tile launchers
 _API_INC += _PLAN + [os.path.join(HERE, "csrc", "hmx_round.h")]      # (hmx_round.h: the round plan and ledger of update_R / head_pass, hmx_api.cpp only)
+_API_INC += [os.path.join(HERE, "csrc", "hmx_xfer_pool.h")]      # (the host threads of the host matrix seam, hmx_api_xfer.inc: host code only)
 _RANKSUM = [os.path.join(HERE, "csrc", f) for f in ("hmx_ranksum.h", "hmx_ranksum_plan.h")] + [os.path.join(HERE, "..", "include", "harmony_mi355x_ranksum.h")]      # the rank sums: hmx_ranksum.hip and hmx_api.cpp only
 _API_INC += _RANKSUM
 _GRAPH = [os.path.join(HERE, "csrc", "hmx_graph.h"), os.path.join(HERE, "..", "include", "harmony_mi355x_graph.h"), os.path.join(HERE, "..", "include", "harmony_mi355x_snn.h")]      # the neighbour graph and the SNN graph: hmx_graph.hip and hmx_api.cpp only

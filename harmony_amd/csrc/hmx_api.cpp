@@ -19,6 +19,7 @@
 #include "hmx_ranksum.h"
 #include "hmx_ranksum_plan.h"
 #include "hmx_graph.h"
+#include "hmx_xfer_pool.h"
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>
@@ -38,6 +39,7 @@
 #include <set>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 using namespace hmx;
@@ -104,11 +106,11 @@ RcclApi* rccl_api(std::string* err) {
 struct ChainGate { std::mutex mu; std::map<int, hipEvent_t> last; std::map<int, const void*> owner; };
 ChainGate& chain_gate() { static ChainGate g; return g; }
 
-bool host_pin_enabled() { const char* e = getenv("HMX_PIN"); return !(e && atoi(e) == 0); }
 double now_ms() {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
+#include "hmx_api_xfer.inc"
 #include "hmx_api_seam.inc"
 #include "hmx_api_kmeans.inc"
 #include "hmx_api_refarith.inc"
@@ -221,17 +223,13 @@ int hmx_comm_allreduce_host(hmx_ctx* ctx, double* inout, int32_t count, int32_t 
   RcclApi* api = rccl_api(nullptr);
   if (ctx->device >= 0) HIPCHK(hipSetDevice(ctx->device));
   if (!ctx->L.stream) { HIPCHK(hipStreamCreateWithFlags(&ctx->L.stream, hipStreamNonBlocking)); ctx->own_stream = true; }
-  double* d = nullptr;
-  HIPCHK(hipMalloc((void**)&d, sizeof(double) * (size_t)count));
-  hipError_t e = hipMemcpyAsync(d, inout, sizeof(double) * (size_t)count, hipMemcpyHostToDevice, ctx->L.stream);
-  ncclResult_t r = ncclSuccess;
-  if (e == hipSuccess) r = api->AllReduce(d, d, (size_t)count, ncclFloat64, op == 0 ? ncclSum : op == 1 ? ncclMax : ncclMin, ctx->comm, ctx->L.stream);
-  if (e == hipSuccess && r == ncclSuccess) e = hipMemcpyAsync(inout, d, sizeof(double) * (size_t)count, hipMemcpyDeviceToHost, ctx->L.stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->L.stream);
-  (void)hipFree(d);
-  if (r != ncclSuccess) return fail(ctx, HMX_ERR_COMM, "ncclAllReduce failed");
-  if (e != hipSuccess) return fail(ctx, HMX_ERR_DEVICE, hipGetErrorString(e));
-  return 0;
+  const auto dev = [&](hipError_t e) { return e == hipSuccess ? 0 : fail(ctx, HMX_ERR_DEVICE, hipGetErrorString(e)); };
+  CallBufs bufs; double* d;
+  HIPCHK(bufs.get(&d, (size_t)count));
+  CHK(dev(upload(d, inout, (size_t)count, ctx->L.stream)));
+  if (api->AllReduce(d, d, (size_t)count, ncclFloat64, op == 0 ? ncclSum : op == 1 ? ncclMax : ncclMin, ctx->comm, ctx->L.stream) != ncclSuccess) return fail(ctx, HMX_ERR_COMM, "ncclAllReduce failed");
+  CHK(dev(download(inout, d, (size_t)count, ctx->L.stream)));
+  return dev(hipStreamSynchronize(ctx->L.stream));
 }
 #include "hmx_api_p2p.inc"
 #include "hmx_api_setup.inc"

@@ -1,39 +1,11 @@
 // hmx_api_call.inc -- part of hmx_api.cpp (included there, ONE translation unit, ahead of every section of a call that keeps no state on the
 // handle): the call seam.  What such a call needs and shares with its siblings, in one flat layer that no feature section adds to: its device
-// and stream, its device buffers and their typed copies, the ingest of a matrix of rows and the argument checks, the rows a metric scores (the
-// caller's X or the handle's own embedding), the exact search the "search then score" calls start with, and what the two graph calls share --
-// the check of neighbour lists, the transposed lists and the emit of a CSR matrix.  (The count-matrix calls' seam: hmx_api_csr.inc.)
+// and stream, the ingest of a matrix of rows and the argument checks, the rows a metric scores (the caller's X or the handle's own embedding),
+// the exact search the "search then score" calls start with, and what the two graph calls share -- the check of neighbour lists, the
+// transposed lists and the emit of a CSR matrix.  (A call's device buffers and their typed copies: CallBufs, hmx_api_seam.inc; the
+// count-matrix calls' seam: hmx_api_csr.inc.)
 
 namespace {
-
-// ---- copies between host and HBM, typed: the byte count follows from the pointers, whose elements must agree in size and kind; a count of 0
-// queues nothing (an empty vector's data() may be null) ----------------------------------------------------------------------------------------
-template <class D, class S> constexpr bool same_layout() { return sizeof(D) == sizeof(S) && std::is_floating_point<D>::value == std::is_floating_point<S>::value; }
-template <class D, class S> hipError_t upload(D* dev, const S* host, size_t count, hipStream_t st) {
-  static_assert(same_layout<D, S>(), "host and device elements differ");
-  return count ? hipMemcpyAsync(dev, host, count * sizeof(D), hipMemcpyHostToDevice, st) : hipSuccess;
-}
-template <class H, class D> hipError_t download(H* host, const D* dev, size_t count, hipStream_t st) {
-  static_assert(same_layout<H, D>(), "host and device elements differ");
-  return count ? hipMemcpyAsync(host, dev, count * sizeof(D), hipMemcpyDeviceToHost, st) : hipSuccess;
-}
-template <class T> hipError_t zero_fill(T* dev, size_t count, hipStream_t st) { return count ? hipMemsetAsync(dev, 0, count * sizeof(T), st) : hipSuccess; }
-
-struct CallBufs {        // device buffers of one call
-  std::vector<void*> v;
-  ~CallBufs() { for (void* p : v) (void)hipFree(p); }
-  template <class T> hipError_t get(T** p, size_t count) {
-    void* q = nullptr;
-    hipError_t e = hipMalloc(&q, std::max<size_t>(count, 1) * sizeof(T));
-    if (e == hipSuccess) v.push_back(q);
-    *p = (T*)q;
-    return e;
-  }
-  template <class T, class S> hipError_t put(T** p, const S* host, size_t count, hipStream_t st) {      // get, then upload
-    const hipError_t e = get(p, count);
-    return e != hipSuccess ? e : upload(*p, host, count, st);
-  }
-};
 
 int call_device(hmx_ctx* ctx) {
   int ndev = 0;

@@ -13,13 +13,13 @@ int hmx_debug_seq_oe(const float* R, int64_t n, int32_t K, const int32_t* level,
   for (int64_t i = 0; i < n; i++) if (level[i] < 0 || level[i] >= B) return HMX_ERR_ARG;
   for (int c = 0; c < nchains; c++) if (chain_off[c] < 0 || chain_cnt[c] < 0 || (int64_t)chain_off[c] + chain_cnt[c] > nlist) return HMX_ERR_ARG;
   hmx_ctx* ctx = hmx_create();
-  float* dR = nullptr; int* dl = nullptr; int* dlev = nullptr; int* dq = nullptr;
   auto run = [&]() -> int {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(ctx, HMX_ERR_DEVICE, "no HIP device");
     HIPCHK(hipStreamCreateWithFlags(&ctx->L.stream, hipStreamNonBlocking)); ctx->own_stream = true;
-    HIPCHK(hipMalloc((void**)&dR, sizeof(float) * (size_t)n * K)); HIPCHK(hipMalloc((void**)&dl, sizeof(int) * (size_t)nlist));
-    HIPCHK(hipMalloc((void**)&dlev, sizeof(int) * (size_t)n)); HIPCHK(hipMalloc((void**)&dq, sizeof(int) * (size_t)B));
+    CallBufs bufs; float* dR; int* dl; int* dlev; int* dq;
+    HIPCHK(bufs.get(&dR, (size_t)n * K)); HIPCHK(bufs.get(&dl, (size_t)nlist));
+    HIPCHK(bufs.get(&dlev, (size_t)n)); HIPCHK(bufs.get(&dq, (size_t)B));
     std::vector<int> ident(B); std::iota(ident.begin(), ident.end(), 0);
     CHK(h2d(ctx, dR, R, (size_t)n * K)); CHK(h2d(ctx, dl, list, (size_t)nlist)); CHK(h2d(ctx, dlev, level, (size_t)n)); CHK(h2d(ctx, dq, ident.data(), (size_t)B));
     ctx->K = K; ctx->B = B; ctx->seq_passes = passes; ctx->seq_stats = true;
@@ -36,7 +36,6 @@ int hmx_debug_seq_oe(const float* R, int64_t n, int32_t K, const int32_t* level,
     return 0;
   };
   const int st = run();
-  for (void* q : {(void*)dR, (void*)dl, (void*)dlev, (void*)dq}) if (q) (void)hipFree(q);
   hmx_destroy(ctx);
   return st;
 }
@@ -45,12 +44,12 @@ int hmx_debug_seq_arr(const float* T, int64_t n, int32_t narr, int32_t seg_terms
   if (!T || !total || n <= 0 || narr <= 0 || narr > 64 || seg_terms < 0 || passes < 2) return HMX_ERR_ARG;
   if (seg_terms == 0 && (narr != 3 || n < 4)) return HMX_ERR_ARG;
   hmx_ctx* ctx = hmx_create();
-  float* dT = nullptr;
   auto run = [&]() -> int {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(ctx, HMX_ERR_DEVICE, "no HIP device");
     HIPCHK(hipStreamCreateWithFlags(&ctx->L.stream, hipStreamNonBlocking)); ctx->own_stream = true;
-    HIPCHK(hipMalloc((void**)&dT, sizeof(float) * (size_t)n * narr));
+    CallBufs bufs; float* dT;
+    HIPCHK(bufs.get(&dT, (size_t)n * narr));
     CHK(h2d(ctx, dT, T, (size_t)n * narr));
     if (seg_terms == 0) {
       // the one-launch form (k_seq_obj_fused, round 6): segments of 32 terms in registers, `passes` passes inside launches of at most 8, the scans between
@@ -88,7 +87,6 @@ int hmx_debug_seq_arr(const float* T, int64_t n, int32_t narr, int32_t seg_terms
     return 0;
   };
   const int st = run();
-  if (dT) (void)hipFree(dT);
   hmx_destroy(ctx);
   return st;
 }
@@ -317,82 +315,27 @@ int64_t hmx_get_matrix(hmx_ctx* ctx, const char* field, void* out, int32_t dtype
   if (!out || cap < cnt) return cnt;
   const float* src = (f == "R") ? ctx->D.R : (f == "Z_corr" ? ctx->D.Zc : ctx->D.Zo);
   // a mapped query keeps no R: its rows are recomputed from Z_orig into a buffer that lives for this call only
-  struct TmpR { float* p = nullptr; ~TmpR() { if (p) (void)hipFree(p); } } tmpR;
+  CallBufs tmp;
   if (ctx->query_done && f == "R") {
-    if (hipMalloc((void**)&tmpR.p, sizeof(float) * (size_t)cnt) != hipSuccess) { (void)hipGetLastError(); ctx->err = "out of device memory for R"; return -1; }
-    if (query_R_rows(ctx, tmpR.p)) return -1;
-    src = tmpR.p;
+    float* rows;
+    if (tmp.get(&rows, (size_t)cnt) != hipSuccess) { (void)hipGetLastError(); ctx->err = "out of device memory for R"; return -1; }
+    if (query_R_rows(ctx, rows)) return -1;
+    src = rows;
   }
   const int ws = (f == "R") ? w : ctx->D.zs;
   const int f32 = dtype == HMX_F32;
-  const size_t esz = f32 ? 4 : 8;
   const double t0 = now_ms();
-  hipError_t e = hipSuccess;
+  hipError_t e;
   if (location == HMX_DEVICE) {
     l_convert_out(ctx->L, src, out, f32, ctx->D.invperm, ctx->D.n, w, ws);
     e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->L.stream);
-  } else if (xfer_mode() == 2 && xfer_ring(ctx->device).ensure()) {
-    // conversion -> HBM staging slab -> DMA into a page-locked ring slot -> host threads copy the slot into the caller's (fresh, pageable)
-    // matrix, touching its pages in parallel, while the next slots are on their way
-    XferRing& ring = xfer_ring(ctx->device);
-    std::lock_guard<std::mutex> ring_lock(ring.mu);
-    XferPool pool; pool.start(xfer_threads());
-    const int64_t slab = std::max<int64_t>(1, (int64_t)XferRing::SLOT / ((int64_t)esz * w));
-    constexpr int NB = XferRing::NB, LAG = NB - 1;
-    hipStream_t cs = ring.cs;
-    hipEvent_t* conv = ring.ev_a; hipEvent_t* copied = ring.ev_b; hipEvent_t* arrived = ring.ev_slot;
-    const int nslabs = (int)((ctx->N + slab - 1) / slab);
-    auto drain = [&](int j) {          // slab j has arrived in its ring slot: out of the ring, into the caller's matrix
-      const int64_t s0 = (int64_t)j * slab, c = std::min<int64_t>(slab, ctx->N - s0);
-      hipError_t ee = hipEventSynchronize(arrived[j % NB]);
-      if (ee == hipSuccess) pool.copy((char*)out + (size_t)s0 * w * esz, ring.slot[j % NB], (size_t)c * w * esz);
-      return ee;
-    };
-    for (int it = 0; it < nslabs && e == hipSuccess; it++) {
-      const int64_t s0 = (int64_t)it * slab, c = std::min<int64_t>(slab, ctx->N - s0);
-      const int b = it & 1;
-      if (it >= 2) e = hipStreamWaitEvent(ctx->L.stream, copied[b], 0);   // the slab's previous contents have left for the host
-      if (e == hipSuccess) { l_convert_out(ctx->L, src, ring.stage[b], f32, ctx->D.invperm + s0, (int)c, w, ws); e = hipGetLastError(); }
-      if (e == hipSuccess) e = hipEventRecord(conv[b], ctx->L.stream);
-      if (e == hipSuccess) e = hipStreamWaitEvent(cs, conv[b], 0);
-      // (ring slot it % NB was drained by the host in iteration it - NB + LAG, i.e. before this point)
-      if (e == hipSuccess) e = hipMemcpyAsync(ring.slot[it % NB], ring.stage[b], (size_t)c * w * esz, hipMemcpyDeviceToHost, cs);
-      if (e == hipSuccess) e = hipEventRecord(copied[b], cs);
-      if (e == hipSuccess) e = hipEventRecord(arrived[it % NB], cs);
-      if (e == hipSuccess && it >= LAG) e = drain(it - LAG);
-    }
-    for (int j = std::max(0, nslabs - LAG); j < nslabs && e == hipSuccess; j++) e = drain(j);
-    (void)hipStreamSynchronize(cs);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->L.stream);
   } else {
-    const int64_t slab = std::max<int64_t>(1, (int64_t)(128ll << 20) / ((int64_t)esz * w));
-    const int64_t scnt = std::min<int64_t>(slab, ctx->N);
-    void* stage[2] = {nullptr, nullptr}; hipStream_t cs = nullptr; hipEvent_t conv[2] = {nullptr, nullptr}, copied[2] = {nullptr, nullptr};
-    const bool pinned = xfer_mode() >= 1 && hipHostRegister(out, (size_t)cnt * esz, hipHostRegisterDefault) == hipSuccess;     // (see hmx_setup_ex)
-    if (!pinned) (void)hipGetLastError();
-    e = hipStreamCreateWithFlags(&cs, hipStreamNonBlocking);
-    for (int i = 0; i < 2 && e == hipSuccess; i++) {
-      e = hipMalloc(&stage[i], (size_t)scnt * w * esz);
-      if (e == hipSuccess) e = hipEventCreateWithFlags(&conv[i], hipEventDisableTiming);
-      if (e == hipSuccess) e = hipEventCreateWithFlags(&copied[i], hipEventDisableTiming);
-    }
-    int it = 0;
-    for (int64_t s0 = 0; s0 < ctx->N && e == hipSuccess; s0 += slab, it++) {
-      const int64_t c = std::min<int64_t>(slab, ctx->N - s0);
-      const int b = it & 1;
-      if (it >= 2) e = hipStreamWaitEvent(ctx->L.stream, copied[b], 0);   // the slab's previous contents have left for the host
-      if (e == hipSuccess) { l_convert_out(ctx->L, src, stage[b], f32, ctx->D.invperm + s0, (int)c, w, ws); e = hipGetLastError(); }
-      if (e == hipSuccess) e = hipEventRecord(conv[b], ctx->L.stream);
-      if (e == hipSuccess) e = hipStreamWaitEvent(cs, conv[b], 0);
-      if (e == hipSuccess) e = hipMemcpyAsync((char*)out + (size_t)s0 * w * esz, stage[b], (size_t)c * w * esz, hipMemcpyDeviceToHost, cs);
-      if (e == hipSuccess) e = hipEventRecord(copied[b], cs);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(cs);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->L.stream);
-    for (int i = 0; i < 2; i++) { if (stage[i]) (void)hipFree(stage[i]); if (conv[i]) (void)hipEventDestroy(conv[i]); if (copied[i]) (void)hipEventDestroy(copied[i]); }
-    if (cs) (void)hipStreamDestroy(cs);
-    if (pinned) (void)hipHostUnregister(out);
+    const size_t cell = (size_t)w * (f32 ? 4 : 8);
+    XferPipe pipe;
+    e = pipe.open(ctx->device, out, ctx->N, cell, ctx->xfer_slab_bytes);
+    if (e == hipSuccess) e = xfer_egress(pipe, ctx->L.stream, out, ctx->N, cell, [&](void* stage, int64_t s0, int64_t c) {
+      l_convert_out(ctx->L, src, stage, f32, ctx->D.invperm + s0, (int)c, w, ws); return hipGetLastError(); });
   }
   if (e != hipSuccess) { ctx->err = hipGetErrorString(e); return -1; }
   ctx->timers["egress_" + f] = now_ms() - t0;

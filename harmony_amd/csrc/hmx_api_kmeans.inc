@@ -31,41 +31,42 @@ int kmeans_centers(hmx_ctx* ctx) {
     const int64_t n = ctx->N;
     int A = (int)std::max<int64_t>(1, std::min<int64_t>(K, (int64_t)(64ll << 20) / (4 * std::max<int64_t>(n, 1))));
     A = std::max(1, std::min(A, 12288 / d));   // anchor rows of a batch live in LDS (<= 48 KB)
-    float* d_u; HIPCHK(hipMalloc((void**)&d_u, sizeof(float) * (size_t)A * (size_t)n));
+    CallBufs bufs; float* d_u; HIPCHK(bufs.get(&d_u, (size_t)A * (size_t)n));
     std::vector<float> hu((size_t)A * (size_t)n);
-    int st = 0;
-    for (int a0 = 0; a0 < K && !st; a0 += A) {
+    const auto race = [&](int a0, int na, int first, const unsigned* excl, int nexcl) {
+      l_seed_race_u(ctx->L, D, d_u, a0, na, first, (uint64_t)ctx->goff, excl, nexcl);
+      return hipGetLastError() == hipSuccess ? 0 : fail(ctx, HMX_ERR_DEVICE, "seed race launch failed");
+    };
+    for (int a0 = 0; a0 < K; a0 += A) {
       const int na = std::min(A, K - a0);
       for (int a = 0; a < na; a++)
         for (int64_t g = 0; g < ctx->N_global; g++) {
           const float u = ctx->rrng.arma_randu();
           if (g >= ctx->goff && g < ctx->goff + n) hu[(size_t)a * n + (size_t)(g - ctx->goff)] = u;
         }
-      st = h2d(ctx, d_u, hu.data(), (size_t)na * (size_t)n);
-      if (!st) st = h2d(ctx, D.seedmin, sentinel.data(), (size_t)K);
-      if (!st) { l_seed_race_u(ctx->L, D, d_u, a0, na, 0, (uint64_t)ctx->goff, nullptr, 0); if (hipGetLastError() != hipSuccess) st = fail(ctx, HMX_ERR_DEVICE, "seed race launch failed"); }
-      if (!st) st = allreduce(ctx, D.seedmin, K, 2);
-      if (!st) st = d2h(ctx, win.data(), D.seedmin, (size_t)K);
-      for (int i = a0; i < a0 + na && !st; i++) {   // duplicates in cluster order (:38-43)
-        if (win[i] == SEED_SENTINEL) { st = fail(ctx, HMX_ERR_STATE, "centroid seeding found no candidate cell"); break; }
+      CHK(h2d(ctx, d_u, hu.data(), (size_t)na * (size_t)n));
+      CHK(h2d(ctx, D.seedmin, sentinel.data(), (size_t)K));
+      CHK(race(a0, na, 0, nullptr, 0));
+      CHK(allreduce(ctx, D.seedmin, K, 2));
+      CHK(d2h(ctx, win.data(), D.seedmin, (size_t)K));
+      for (int i = a0; i < a0 + na; i++) {   // duplicates in cluster order (:38-43)
+        if (win[i] == SEED_SENTINEL) return fail(ctx, HMX_ERR_STATE, "centroid seeding found no candidate cell");
         unsigned g = (unsigned)(win[i] & 0xffffffffu);
         if (sup.count(g)) {
           std::vector<unsigned> ex(sup.begin(), sup.end());
-          st = h2d(ctx, d_excl, ex.data(), ex.size());
-          if (!st) st = h2d(ctx, D.seedmin, sentinel.data(), (size_t)K);
-          if (!st) { l_seed_race_u(ctx->L, D, d_u, a0, na, i - a0, (uint64_t)ctx->goff, d_excl, (int)ex.size()); if (hipGetLastError() != hipSuccess) st = fail(ctx, HMX_ERR_DEVICE, "seed race launch failed"); }
-          if (!st) st = allreduce(ctx, D.seedmin, K, 2);
+          CHK(h2d(ctx, d_excl, ex.data(), ex.size()));
+          CHK(h2d(ctx, D.seedmin, sentinel.data(), (size_t)K));
+          CHK(race(a0, na, i - a0, d_excl, (int)ex.size()));
+          CHK(allreduce(ctx, D.seedmin, K, 2));
           std::vector<unsigned long long> w2(K);
-          if (!st) st = d2h(ctx, w2.data(), D.seedmin, (size_t)K);
-          if (!st && w2[i] == SEED_SENTINEL) st = fail(ctx, HMX_ERR_STATE, "centroid seeding ran out of distinct cells");
+          CHK(d2h(ctx, w2.data(), D.seedmin, (size_t)K));
+          if (w2[i] == SEED_SENTINEL) return fail(ctx, HMX_ERR_STATE, "centroid seeding ran out of distinct cells");
           g = (unsigned)(w2[i] & 0xffffffffu);
         }
         sup.insert(g);
         gcells[i] = (long long)g;
       }
     }
-    (void)hipFree(d_u);
-    if (st) return st;
   } else {
   // exponential race for every anchor in one pass (:24-34)
   CHK(h2d(ctx, D.seedmin, sentinel.data(), (size_t)K));

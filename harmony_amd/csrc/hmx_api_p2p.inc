@@ -75,9 +75,9 @@ static void p2p_auto(hmx_ctx* ctx, RcclApi* api, int rank, int world) {
   if (!ctx->L.stream) { if (hipStreamCreateWithFlags(&ctx->L.stream, hipStreamNonBlocking) != hipSuccess) return give_up("no stream"); ctx->own_stream = true; }
   uint8_t mine[HMX_P2P_HANDLE_BYTES] = {};
   long long ok = hmx_p2p_export(ctx, mine) == 0 ? 1 : 0;    // (a rank that cannot export still takes part in the collectives)
-  uint8_t* dev = nullptr; long long* flag = nullptr;
+  CallBufs bufs; uint8_t* dev = nullptr; long long* flag = nullptr;
   std::vector<uint8_t> all((size_t)world * HMX_P2P_HANDLE_BYTES);
-  if (hipMalloc((void**)&dev, all.size()) != hipSuccess || hipMalloc((void**)&flag, 8) != hipSuccess) return give_up("hipMalloc");
+  if (bufs.get(&dev, all.size()) != hipSuccess || bufs.get(&flag, 1) != hipSuccess) return give_up("hipMalloc");
   bool comm_ok = hipMemcpyAsync(dev + (size_t)rank * HMX_P2P_HANDLE_BYTES, mine, sizeof(mine), hipMemcpyHostToDevice, ctx->L.stream) == hipSuccess &&
                  api->AllGather(dev + (size_t)rank * HMX_P2P_HANDLE_BYTES, dev, HMX_P2P_HANDLE_BYTES, ncclInt8, ctx->comm, ctx->L.stream) == ncclSuccess &&
                  hipMemcpyAsync(all.data(), dev, all.size(), hipMemcpyDeviceToHost, ctx->L.stream) == hipSuccess &&
@@ -92,7 +92,6 @@ static void p2p_auto(hmx_ctx* ctx, RcclApi* api, int rank, int world) {
   agree();                                                                       // everyone exported (also a barrier)
   if (comm_ok && ok) { ok = hmx_p2p_connect(ctx, rank, world, all.data()) == 0 ? 1 : 0; agree(); }     // everyone connected
   if (comm_ok && ok) { ok = hmx_p2p_selftest(ctx) == 0 ? 1 : 0; agree(); }                             // everyone heard everyone
-  (void)hipFree(dev); (void)hipFree(flag);
   if (!comm_ok) return give_up("bootstrap collectives failed");
   if (!ok) return give_up(ctx->p2p_note.empty() ? "a rank failed" : ctx->p2p_note + " (on some rank)");
   (void)hmx_p2p_enable(ctx, 1);
@@ -165,6 +164,7 @@ int hmx_set_int(hmx_ctx* ctx, const char* field, int64_t v) {
   else if (f == "seq_strict") { ctx->seq_strict = v != 0; if (v && ctx->seq_max_passes < 64) ctx->seq_max_passes = 64; }
   else if (f == "seq_max_passes") { if (v < 2 || v > 256) return fail(ctx, HMX_ERR_ARG, "seq_max_passes: 2..256"); ctx->seq_max_passes = (int)v; }
   else if (f == "project_slab_bytes") { if (v < 0) return fail(ctx, HMX_ERR_ARG, "project_slab_bytes: 0 (the default) or a positive byte count"); ctx->project_slab_bytes = v; }
+  else if (f == "xfer_slab_bytes") { if (v < 0) return fail(ctx, HMX_ERR_ARG, "xfer_slab_bytes: 0 (the default) or a positive byte count"); ctx->xfer_slab_bytes = v; }
   else if (f == "ranksum_list_bytes") { if (v < 0) return fail(ctx, HMX_ERR_ARG, "ranksum_list_bytes: 0 (the default) or a positive byte count"); ctx->ranksum_list_bytes = v; }
   else if (f == "device") ctx->device = (int)v;
   else if (f == "profile") { ctx->profile = (int)(v < 0 ? 0 : v > 2 ? 2 : v); ctx->prof_update_ms = 0; ctx->prof_update_launches = 0; ctx->prof_update_cells = 0; ctx->prof_update_steps = 0; ctx->ev_used = 0;

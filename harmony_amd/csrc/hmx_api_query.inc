@@ -22,28 +22,18 @@ static int query_sums(hmx_ctx* ctx, QueryDev Q, int summary, const std::vector<I
   const int nsl = (total + QUERY_SLICE - 1) / QUERY_SLICE;
   Q.slice = (total + nsl - 1) / nsl;
   Q.nchunks = (int)chunks.size();
-  Item* dch = nullptr; int* dqc = nullptr; double* dres = nullptr;
-  Q.part = nullptr;
-  hipError_t e = hipMalloc((void**)&dch, sizeof(Item) * std::max<size_t>(chunks.size(), 1));
-  if (e == hipSuccess) e = hipMalloc((void**)&dqc, sizeof(int) * qchunk.size());
-  if (e == hipSuccess) e = hipMalloc((void**)&Q.part, sizeof(double) * std::max<size_t>((size_t)Q.nchunks * total, 1));
-  if (e == hipSuccess) e = hipMalloc((void**)&dres, sizeof(double) * (size_t)nq * total);
-  if (e == hipSuccess && !chunks.empty()) e = hipMemcpyAsync(dch, chunks.data(), sizeof(Item) * chunks.size(), hipMemcpyHostToDevice, ctx->L.stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(dqc, qchunk.data(), sizeof(int) * qchunk.size(), hipMemcpyHostToDevice, ctx->L.stream);
-  Q.chunks = dch;
-  if (e == hipSuccess && Q.nchunks) { l_query_stats(ctx->L, Q, summary); e = hipGetLastError(); }
-  if (e == hipSuccess) { l_query_fold(ctx->L, Q.part, dqc, nq, total, dres); e = hipGetLastError(); }
-  int st = 0;
-  if (e == hipSuccess && summary) st = allreduce(ctx, dres, (int64_t)nq * total, 1);      // sharded handle: the global summary on every rank
+  const auto dev = [&](hipError_t e) { return e == hipSuccess ? 0 : fail(ctx, HMX_ERR_DEVICE, std::string("query statistics: ") + hipGetErrorString(e)); };
+  hipStream_t st = ctx->L.stream; CallBufs bufs; Item* dch; int* dqc; double* dres;
   out.assign((size_t)nq * total, 0.0);
-  if (e == hipSuccess && !st) e = hipMemcpyAsync(out.data(), dres, sizeof(double) * out.size(), hipMemcpyDeviceToHost, ctx->L.stream);
-  if (e == hipSuccess && !st) e = hipStreamSynchronize(ctx->L.stream);
-  (void)hipStreamSynchronize(ctx->L.stream);
-  void* ps[] = {dch, dqc, Q.part, dres};
-  for (void* p : ps) if (p) (void)hipFree(p);
-  if (st) return st;
-  if (e != hipSuccess) return fail(ctx, HMX_ERR_DEVICE, std::string("query statistics: ") + hipGetErrorString(e));
-  return 0;
+  CHK(dev(bufs.get(&dch, chunks.size()))); CHK(dev(bufs.get(&dqc, qchunk.size())));
+  CHK(dev(bufs.get(&Q.part, (size_t)Q.nchunks * total))); CHK(dev(bufs.get(&dres, out.size())));
+  CHK(dev(upload(dch, chunks.data(), chunks.size(), st))); CHK(dev(upload(dqc, qchunk.data(), qchunk.size(), st)));
+  Q.chunks = dch;
+  if (Q.nchunks) { l_query_stats(ctx->L, Q, summary); CHK(dev(hipGetLastError())); }
+  l_query_fold(ctx->L, Q.part, dqc, nq, total, dres); CHK(dev(hipGetLastError()));
+  if (summary) CHK(allreduce(ctx, dres, (int64_t)nq * total, 1));      // sharded handle: the global summary on every rank
+  CHK(dev(download(out.data(), dres, out.size(), st)));
+  return dev(hipStreamSynchronize(st));
 }
 
 // the reference summary of a fitted handle: res[k][0..d) = sum_i R[k,i] Z_corr[:,i], res[k][d] = sum_i R[k,i] over the current rows

@@ -1,109 +1,32 @@
-// hmx_api_seam.inc -- part of hmx_api.cpp (included there, ONE translation unit): host side of the R seam: page-locked ring, host threads, slab pipeline (hmx_setup / hmx_get_matrix with host buffers); R-compatible stream helpers
-// ---- host side of the R seam (R/ui.R:178-183, 292-295: a pageable fp64 matrix in, a fresh pageable fp64 matrix out) ---------------------
-// Page-locking the caller's 400 MB matrix for one transfer costs more than the transfer (every page is faulted in and pinned by ONE thread
-// before the first byte moves).  Default path instead: a small ring of page-locked buffers, allocated once per process, and a few host
-// threads that move the bytes between the caller's matrix and the ring slot by slot while the DMA engine moves the previous slots --
-// on egress the threads are also the ones that first touch the fresh destination pages, in parallel.  HMX_XFER=pin: register the caller's
-// buffer (the earlier path); HMX_PIN=0: plain pageable copies; HMX_XFER_THREADS: threads (default 8).
-struct XferPool {
-  // (the workers SPIN between the slots of one transfer -- a transfer lasts ~10-20 ms and hands out a slot every ~0.5 ms; waking sleeping
-  //  threads through a condition variable for every slot cost more than the copies)
-  std::vector<std::thread> th;
-  const char* src = nullptr; char* dst = nullptr; size_t bytes = 0;
-  std::atomic<size_t> next{0};
-  std::atomic<int> gen{0}, running{0};
-  std::atomic<bool> stop{false};
-  static constexpr size_t CHUNK = 1 << 20;
-  void work() {
-    for (;;) {
-      const size_t off = next.fetch_add(CHUNK);
-      if (off >= bytes) break;
-      memcpy(dst + off, src + off, std::min(CHUNK, bytes - off));
-    }
+// hmx_api_seam.inc -- part of hmx_api.cpp (included there, ONE translation unit): typed copies and the device buffers of one call (CallBufs); the handle (hmx_ctx); head pass, objective series and the other helpers the clustering sections share
+// ---- copies between host and HBM, typed: the byte count follows from the pointers, whose elements must agree in size and kind; a count of 0
+// queues nothing (an empty vector's data() may be null) ----------------------------------------------------------------------------------------
+template <class D, class S> constexpr bool same_layout() { return sizeof(D) == sizeof(S) && std::is_floating_point<D>::value == std::is_floating_point<S>::value; }
+template <class D, class S> hipError_t upload(D* dev, const S* host, size_t count, hipStream_t st) {
+  static_assert(same_layout<D, S>(), "host and device elements differ");
+  return count ? hipMemcpyAsync(dev, host, count * sizeof(D), hipMemcpyHostToDevice, st) : hipSuccess;
+}
+template <class H, class D> hipError_t download(H* host, const D* dev, size_t count, hipStream_t st) {
+  static_assert(same_layout<H, D>(), "host and device elements differ");
+  return count ? hipMemcpyAsync(host, dev, count * sizeof(D), hipMemcpyDeviceToHost, st) : hipSuccess;
+}
+template <class T> hipError_t zero_fill(T* dev, size_t count, hipStream_t st) { return count ? hipMemsetAsync(dev, 0, count * sizeof(T), st) : hipSuccess; }
+
+struct CallBufs {        // device buffers of one call: freed when it returns, on every path
+  std::vector<void*> v;
+  ~CallBufs() { for (void* p : v) (void)hipFree(p); }
+  template <class T> hipError_t get(T** p, size_t count) {
+    void* q = nullptr;
+    hipError_t e = hipMalloc(&q, std::max<size_t>(count, 1) * sizeof(T));
+    if (e == hipSuccess) v.push_back(q);
+    *p = (T*)q;
+    return e;
   }
-  void loop() {
-    int seen = 0;
-    for (;;) {
-      int g;
-      while ((g = gen.load(std::memory_order_acquire)) == seen) {
-        if (stop.load(std::memory_order_relaxed)) return;
-        __builtin_ia32_pause();
-      }
-      seen = g;
-      work();
-      running.fetch_sub(1, std::memory_order_release);
-    }
-  }
-  void start(int T) {      // (a thread that cannot be created is simply missing: the caller works too, copy() falls back to a plain memcpy without helpers)
-    for (int i = 0; i < T; i++) {
-      try { th.emplace_back([this] { loop(); }); } catch (...) { break; }
-    }
-  }
-  void copy(void* d, const void* s_, size_t n) {           // blocking; the caller works too
-    if (th.empty() || n < 4 * CHUNK) { memcpy(d, s_, n); return; }
-    src = (const char*)s_; dst = (char*)d; bytes = n; next.store(0);
-    running.store((int)th.size(), std::memory_order_relaxed);
-    gen.fetch_add(1, std::memory_order_release);
-    work();
-    while (running.load(std::memory_order_acquire) != 0) __builtin_ia32_pause();
-  }
-  ~XferPool() {
-    stop.store(true);
-    for (auto& t : th) t.join();
+  template <class T, class S> hipError_t put(T** p, const S* host, size_t count, hipStream_t st) {      // get, then upload
+    const hipError_t e = get(p, count);
+    return e != hipSuccess ? e : upload(*p, host, count, st);
   }
 };
-int xfer_threads();
-struct XferRing {     // page-locked staging slots + the copy stream, HBM staging slabs and events of a transfer: one set per device and
-                      // process, built (and run through once) on first use, shared by all handles (guarded: one transfer at a time)
-  static constexpr int NB = 4;
-  static constexpr size_t SLOT = (size_t)16 << 20;
-  std::mutex mu, init_mu;
-  void* slot[NB] = {nullptr, nullptr, nullptr, nullptr};
-  void* stage[2] = {nullptr, nullptr};                       // HBM staging slabs (SLOT bytes each)
-  hipStream_t cs = nullptr;
-  hipEvent_t ev_a[2] = {nullptr, nullptr}, ev_b[2] = {nullptr, nullptr}, ev_slot[NB] = {nullptr, nullptr, nullptr, nullptr};
-  bool ok = false, tried = false;
-  bool ensure() {
-    std::lock_guard<std::mutex> lk(init_mu);
-    if (tried) return ok;
-    tried = true;
-    bool good = hipStreamCreateWithFlags(&cs, hipStreamNonBlocking) == hipSuccess;
-    for (int i = 0; i < NB && good; i++) good = hipHostMalloc(&slot[i], SLOT, hipHostMallocDefault) == hipSuccess && hipEventCreateWithFlags(&ev_slot[i], hipEventDisableTiming) == hipSuccess;
-    for (int i = 0; i < 2 && good; i++) good = hipMalloc(&stage[i], SLOT) == hipSuccess && hipEventCreateWithFlags(&ev_a[i], hipEventDisableTiming) == hipSuccess &&
-                                               hipEventCreateWithFlags(&ev_b[i], hipEventDisableTiming) == hipSuccess;
-    // first touch from both sides and one pass through exactly the calls a transfer makes (the CPU faults the slots' pages in on its
-    // first write, the device maps them and sets up its copy queues on the first asynchronous copy): once per process instead of inside
-    // the first matrix's transfer
-    for (int i = 0; i < NB && good; i++) {
-      memset(slot[i], 0, SLOT);
-      good = hipMemcpyAsync(stage[i & 1], slot[i], SLOT, hipMemcpyHostToDevice, cs) == hipSuccess && hipEventRecord(ev_slot[i], cs) == hipSuccess &&
-             hipMemcpyAsync(slot[i], stage[i & 1], SLOT, hipMemcpyDeviceToHost, cs) == hipSuccess && hipEventRecord(ev_a[i & 1], cs) == hipSuccess &&
-             hipEventSynchronize(ev_slot[i]) == hipSuccess;
-    }
-    if (good) good = hipStreamSynchronize(cs) == hipSuccess;
-    if (good) {
-      // ... and once through the helper threads (round 3 measured +16 ms on a process' FIRST threaded transfer and left it unexplained:
-      // thread stacks, first scheduling of eight spinning threads, the cores' clocks): a pool of the size a transfer uses moves 4 slots'
-      // worth of bytes between the slots here, once per process, instead of inside the first matrix's transfer
-      XferPool warm; warm.start(xfer_threads());
-      for (int r = 0; r < 2; r++) for (int i = 0; i + 1 < NB; i += 2) warm.copy(slot[i + 1], slot[i], SLOT);
-    }
-    if (!good) (void)hipGetLastError();
-    return ok = good;
-  }
-};
-XferRing& xfer_ring(int device) { static std::mutex m; static std::map<int, XferRing> rings; std::lock_guard<std::mutex> lk(m); return rings[device]; }
-int xfer_mode() {     // 0 pageable copies, 1 register the caller's buffer, 2 ring of page-locked slots + host threads (default)
-  if (!host_pin_enabled()) return 0;
-  const char* e = getenv("HMX_XFER");
-  if (e && std::string(e) == "pin") return 1;
-  return 2;
-}
-int xfer_threads() {      // (the workers spin while a transfer runs: never more of them than spare cores)
-  const char* e = getenv("HMX_XFER_THREADS");
-  const int t = e ? atoi(e) : 8, spare = (int)std::thread::hardware_concurrency() - 1;
-  return std::max(0, std::min(std::min(t, 64), std::max(spare, 0)));
-}
 
 }  // namespace
 
@@ -257,6 +180,8 @@ struct hmx_ctx {
   bool query_done = false;
   // ---- count projection (hmx_project_counts): the lab field "project_slab_bytes" (0: the default cap) and the slabs the last host-resident call ran
   int64_t project_slab_bytes = 0, project_slabs = 0;
+  // ---- the host matrix seam (hmx_api_xfer.inc): the lab field "xfer_slab_bytes", a cap on the bytes of a staging slab (0: the path's default)
+  int64_t xfer_slab_bytes = 0;
   // ---- rank sums (hmx_rank_sums): the lab field "ranksum_list_bytes" (0: the default budget of a gene block) and the gene blocks the last call ran
   int64_t ranksum_list_bytes = 0, ranksum_blocks = 0;
   // ---- connected components (hmx_graph_components): the hook-and-jump rounds of the last call ("graph:cc_rounds")

@@ -54,83 +54,27 @@ static void combo_order(hmx_ctx* ctx, int64_t N, int32_t C, const std::vector<lo
 static int ingest_Z(hmx_ctx* ctx, const void* Z, int32_t z_dtype, int32_t z_location, int64_t N, int32_t d) {
   Dev& D = ctx->D;
   // Z: d x N (cell-major), double (the R seam, conv_to :41) or float, on the host or already in HBM -> fp32 rows in internal
-  // order.  Host input goes through two HBM staging slabs: the copy of slab s+1 (copy stream) overlaps the conversion of slab s.
+  // order.  Host input goes through the slab pipeline of hmx_api_xfer.inc.
   if (z_location != HMX_DEVICE && xfer_mode() == 2) (void)xfer_ring(ctx->device).ensure();    // (once per process: not part of a matrix's transfer time)
   // (the buffers' first touch by the clears above is allocate_buffers' time, and the first launch of a library kernel in a process loads the
   //  code object -- tens of ms once per process --: neither is the ingest's)
   l_copy(ctx->L, D.Zo, D.Zo, 0); KCHK();
   HIPCHK(hipStreamSynchronize(ctx->L.stream));
-  {
-    const double t_in = now_ms();
-    const int f32 = z_dtype == HMX_F32;
-    const size_t esz = f32 ? 4 : 8;
-    if (z_location == HMX_DEVICE) {
-      l_convert_in(ctx->L, Z, f32, D.Zo, D.invperm, (int)N, d, D.zs); KCHK();
-      HIPCHK(hipStreamSynchronize(ctx->L.stream));
-    } else if (xfer_mode() == 2 && xfer_ring(ctx->device).ensure()) {
-      // ring of page-locked slots: host threads fill slot b while the DMA engine drains the earlier ones and the conversion kernel
-      // consumes what has landed (two HBM staging slabs)
-      XferRing& ring = xfer_ring(ctx->device);
-      std::lock_guard<std::mutex> ring_lock(ring.mu);
-      XferPool pool; pool.start(xfer_threads());
-      const int64_t slab = std::max<int64_t>(1, (int64_t)XferRing::SLOT / ((int64_t)esz * d));
-      hipStream_t cs = ring.cs;
-      hipEvent_t* copied = ring.ev_a; hipEvent_t* used = ring.ev_b; hipEvent_t* left = ring.ev_slot;   // left[b]: slot b's bytes have left for the device
-      ctx->timers["ingest_pinned"] = 2.0;
-      hipError_t e = hipSuccess;
-      int it = 0;
-      for (int64_t s0 = 0; s0 < N && e == hipSuccess; s0 += slab, it++) {
-        const int64_t cnt = std::min<int64_t>(slab, N - s0);
-        const size_t nbytes = (size_t)cnt * d * esz;
-        const int b = it & 1, rb = it % XferRing::NB;
-        if (it >= XferRing::NB) e = hipEventSynchronize(left[rb]);
-        if (e != hipSuccess) break;
-        pool.copy(ring.slot[rb], (const char*)Z + (size_t)s0 * d * esz, nbytes);
-        if (it >= 2) e = hipStreamWaitEvent(cs, used[b], 0);           // the slab's previous conversion has read it
-        if (e == hipSuccess) e = hipMemcpyAsync(ring.stage[b], ring.slot[rb], nbytes, hipMemcpyHostToDevice, cs);
-        if (e == hipSuccess) e = hipEventRecord(left[rb], cs);
-        if (e == hipSuccess) e = hipEventRecord(copied[b], cs);
-        if (e == hipSuccess) e = hipStreamWaitEvent(ctx->L.stream, copied[b], 0);
-        if (e == hipSuccess) { l_convert_in(ctx->L, ring.stage[b], f32, D.Zo, D.invperm + s0, (int)cnt, d, D.zs); e = hipGetLastError(); }
-        if (e == hipSuccess) e = hipEventRecord(used[b], ctx->L.stream);
-      }
-      if (e == hipSuccess) e = hipStreamSynchronize(ctx->L.stream);
-      (void)hipStreamSynchronize(cs);
-      if (e != hipSuccess) return fail(ctx, HMX_ERR_DEVICE, hipGetErrorString(e));
-    } else {
-      const int64_t slab = std::max<int64_t>(1, (int64_t)(128ll << 20) / ((int64_t)esz * d));
-      const int64_t scnt = std::min<int64_t>(slab, N);
-      void* stage[2] = {nullptr, nullptr}; hipStream_t cs = nullptr; hipEvent_t copied[2] = {nullptr, nullptr}, used[2] = {nullptr, nullptr};
-      // The caller's matrix is pageable (R's heap): page-lock it for the duration of the ingest, so that the slab copies are real DMA
-      // at PCIe speed instead of the runtime's staged pageable path (HMX_PIN=0 leaves it pageable; a failed registration is not an error).
-      const bool pinned = xfer_mode() >= 1 && hipHostRegister(const_cast<void*>(Z), (size_t)N * d * esz, hipHostRegisterDefault) == hipSuccess;
-      if (!pinned) (void)hipGetLastError();
-      ctx->timers["ingest_pinned"] = pinned ? 1.0 : 0.0;
-      hipError_t e = hipStreamCreateWithFlags(&cs, hipStreamNonBlocking);
-      for (int i = 0; i < 2 && e == hipSuccess; i++) {
-        e = hipMalloc(&stage[i], (size_t)scnt * d * esz);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&copied[i], hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&used[i], hipEventDisableTiming);
-      }
-      int it = 0;
-      for (int64_t s0 = 0; s0 < N && e == hipSuccess; s0 += slab, it++) {
-        const int64_t cnt = std::min<int64_t>(slab, N - s0);
-        const int b = it & 1;
-        if (it >= 2) e = hipStreamWaitEvent(cs, used[b], 0);           // the slab's previous conversion has read it
-        if (e == hipSuccess) e = hipMemcpyAsync(stage[b], (const char*)Z + (size_t)s0 * d * esz, (size_t)cnt * d * esz, hipMemcpyHostToDevice, cs);
-        if (e == hipSuccess) e = hipEventRecord(copied[b], cs);
-        if (e == hipSuccess) e = hipStreamWaitEvent(ctx->L.stream, copied[b], 0);
-        if (e == hipSuccess) { l_convert_in(ctx->L, stage[b], f32, D.Zo, D.invperm + s0, (int)cnt, d, D.zs); e = hipGetLastError(); }
-        if (e == hipSuccess) e = hipEventRecord(used[b], ctx->L.stream);
-      }
-      if (e == hipSuccess) e = hipStreamSynchronize(ctx->L.stream);
-      for (int i = 0; i < 2; i++) { if (stage[i]) (void)hipFree(stage[i]); if (copied[i]) (void)hipEventDestroy(copied[i]); if (used[i]) (void)hipEventDestroy(used[i]); }
-      if (cs) (void)hipStreamDestroy(cs);
-      if (pinned) (void)hipHostUnregister(const_cast<void*>(Z));
-      if (e != hipSuccess) return fail(ctx, HMX_ERR_DEVICE, hipGetErrorString(e));
-    }
-    ctx->timers["ingest_Z"] = now_ms() - t_in;
+  const double t_in = now_ms();
+  const int f32 = z_dtype == HMX_F32;
+  if (z_location == HMX_DEVICE) {
+    l_convert_in(ctx->L, Z, f32, D.Zo, D.invperm, (int)N, d, D.zs); KCHK();
+    HIPCHK(hipStreamSynchronize(ctx->L.stream));
+  } else {
+    const size_t cell = (size_t)d * (f32 ? 4 : 8);
+    XferPipe pipe;
+    hipError_t e = pipe.open(ctx->device, const_cast<void*>(Z), N, cell, ctx->xfer_slab_bytes);
+    ctx->timers["ingest_pinned"] = (double)pipe.pinned;
+    if (e == hipSuccess) e = xfer_ingest(pipe, ctx->L.stream, Z, N, cell, [&](const void* stage, int64_t s0, int64_t cnt) {
+      l_convert_in(ctx->L, stage, f32, D.Zo, D.invperm + s0, (int)cnt, d, D.zs); return hipGetLastError(); });
+    if (e != hipSuccess) return fail(ctx, HMX_ERR_DEVICE, hipGetErrorString(e));
   }
+  ctx->timers["ingest_Z"] = now_ms() - t_in;
   return 0;
 }
 
@@ -161,14 +105,10 @@ static int design_order(hmx_ctx* ctx, int64_t N, const int32_t* phi_i, const int
   std::vector<long long> nbcount((size_t)B, 0);
   for (int c = 0; c < C; c++) for (int64_t i = 0; i < N; i++) nbcount[codes[(size_t)c * N + i]]++;
   if (ctx->world > 1 || ctx->comm_force) {
-    long long* dtmp; const size_t cnt = (size_t)P + B;
-    HIPCHK(hipMalloc((void**)&dtmp, cnt * sizeof(long long)));
+    CallBufs bufs; long long* dtmp; const size_t cnt = (size_t)P + B;
+    HIPCHK(bufs.get(&dtmp, cnt));
     std::vector<long long> tmp(present); tmp.insert(tmp.end(), nbcount.begin(), nbcount.end());
-    int st = h2d(ctx, dtmp, tmp.data(), cnt);
-    if (!st) st = allreduce(ctx, dtmp, (int64_t)cnt, 0);
-    if (!st) st = d2h(ctx, tmp.data(), dtmp, cnt);
-    (void)hipFree(dtmp);
-    if (st) return st;
+    CHK(h2d(ctx, dtmp, tmp.data(), cnt)); CHK(allreduce(ctx, dtmp, (int64_t)cnt, 0)); CHK(d2h(ctx, tmp.data(), dtmp, cnt));
     std::copy(tmp.begin(), tmp.begin() + P, present.begin());
     std::copy(tmp.begin() + P, tmp.end(), nbcount.begin());
   }
@@ -188,8 +128,8 @@ static int design_order(hmx_ctx* ctx, int64_t N, const int32_t* phi_i, const int
 
 // a flag every rank of a sharded run must share: the minimum over the ranks (one MIN all-reduce of `n` words)
 static int agree_min(hmx_ctx* ctx, long long* flags, size_t n) {
-  long long* dflag;
-  CHK(dalloc(ctx, &dflag, n));
+  CallBufs bufs; long long* dflag;
+  HIPCHK(bufs.get(&dflag, n));
   CHK(h2d(ctx, dflag, flags, n)); CHK(allreduce(ctx, dflag, (int64_t)n, 2)); CHK(d2h(ctx, flags, dflag, n));
   return 0;
 }

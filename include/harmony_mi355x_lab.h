@@ -25,6 +25,9 @@ extern "C" {
  *   result does not depend on it, bit for bit; hmx_get "project_slabs": the slabs the last such call ran);
  *   "ranksum_list_bytes" (the rank sums of harmony_mi355x_ranksum.h: bytes of a gene block's list and sort buffer, 0 = the default 8 GiB; the
  *   result does not depend on it, bit for bit; hmx_get "ranksum_blocks": the gene blocks the last such call ran);
+ *   "xfer_slab_bytes" (host matrices: hmx_setup / hmx_setup_ex / hmx_map_query with HMX_HOST, hmx_get / hmx_get_matrix into a host buffer -- a cap
+ *   on the bytes of a staging slab: a slab holds min(the path's default, this) bytes of whole cells, at least one cell; 0 = the defaults, 16 MiB
+ *   through the ring of page-locked slots and 128 MiB through staging of the call's own; the result does not depend on it, bit for bit);
  *   environment, read by hmx_setup: HMX_GRID, HMX_NREP, HMX_UPD_WPS (2|4), HMX_USIG=0 (general-sigma kernels),
  *   HMX_UPD_THREADS, HMX_UPD_MAXBLOCKS, HMX_STATIC_MAXBLOCKS, HMX_UPD_TPW, HMX_FUSED_FOLD=0, HMX_FOLD_IMPL=split|merged,
  *   HMX_OLDSUM_IMPL=gather|stream1, HMX_MOE_IMPL=v1 (first-generation kernels),

@@ -646,6 +646,123 @@ def test_f32_and_device_pointer_ingest_egress():
     assert ref.timer("ingest_Z") > 0 and ref.timer("egress_Z_corr") > 0
 
 
+# ---- the host matrix seam across slab boundaries (hmx_api_xfer.inc): with "xfer_slab_bytes" = 16384 a slab of the d = 8 ingest holds 256 fp64 /
+# 512 fp32 cells, so the cell counts below are 1 ragged slab, 2 exact slabs, 3 slabs, 6 (more than the ring's 4 slots), 10 with a 1-cell last slab
+XFER_PATHS = {"ring": {}, "register": {"HMX_XFER": "pin"}, "pageable": {"HMX_PIN": "0"}}
+XFER_CELLS = (200, 512, 700, 1300, 2305)
+XFER_D, XFER_K, XFER_SLAB = 8, 16, 16384
+_xfer_memo = {}
+
+
+def _xfer_path(monkeypatch, path):
+    for name in ("HMX_XFER", "HMX_PIN", "HMX_XFER_THREADS"):
+        monkeypatch.delenv(name, raising=False)
+    for name, v in XFER_PATHS[path].items():
+        monkeypatch.setenv(name, v)               # (the library reads the switches per transfer)
+
+
+def _xfer_pinned_ok(path, pinned):
+    return pinned == 2 if path == "ring" else pinned in (0, 1) if path == "register" else pinned == 0     # (a refused registration is not an error)
+
+
+def _xfer_problem(N, dtype, d=XFER_D):
+    """setup arguments with Z as `dtype` on the host, and Z_orig of the same matrix ingested through the device-pointer path, which runs no pipeline"""
+    key = (N, d, np.dtype(dtype).name)
+    if key not in _xfer_memo:
+        import ctypes as C
+        hip = C.CDLL("libamdhip64.so.7")
+        hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
+        hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+        hip.hipFree.argtypes = [C.c_void_p]
+        Z, meta, _ = synth(N, d=d, levels=(3,), seed=11)
+        skw, _ = prepare_setup_args(Z, meta, "cov0", nclust=XFER_K)
+        Zh = np.asfortranarray(skw["Z"], dtype=dtype)
+        dptr = C.c_void_p()
+        assert hip.hipMalloc(C.byref(dptr), Zh.nbytes) == 0
+        assert hip.hipMemcpy(dptr, Zh.ctypes.data, Zh.nbytes, 1) == 0
+        dev = Harmony(seed=1)
+        dev.setup(**dict(skw, Z=(d, N, dtype, dptr.value)))
+        hip.hipFree(dptr)
+        want = dev.getZorig()
+        assert np.array_equal(want, Zh.astype(np.float32).astype(np.float64))
+        want.setflags(write=False)
+        _xfer_memo[key] = (dict(skw, Z=Zh), want)
+    return _xfer_memo[key]
+
+
+@pytest.mark.parametrize("path", list(XFER_PATHS))
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+@pytest.mark.parametrize("N", XFER_CELLS)
+def test_host_ingest_across_slab_boundaries(monkeypatch, N, dtype, path):
+    skw, want = _xfer_problem(N, dtype)
+    _xfer_path(monkeypatch, path)
+    h = Harmony(seed=1)
+    h._set("xfer_slab_bytes", XFER_SLAB)
+    h.setup(**skw)
+    pinned = h.timer("ingest_pinned")
+    h._set("xfer_slab_bytes", 0)                  # (the check's own read is not under test)
+    monkeypatch.undo()
+    np.testing.assert_array_equal(h.getZorig(), want)
+    assert _xfer_pinned_ok(path, pinned), (path, pinned)
+
+
+@pytest.mark.parametrize("path", list(XFER_PATHS))
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+@pytest.mark.parametrize("N", XFER_CELLS)
+def test_host_egress_across_slab_boundaries(monkeypatch, N, dtype, path):
+    skw, _ = _xfer_problem(N, dtype)
+    _xfer_path(monkeypatch, path)
+    h = Harmony(seed=1)
+    h.setup(**skw)
+    h.init_cluster_cpp(np.asfortranarray(skw["Z"][:, :XFER_K], dtype=np.float64))
+    assert h.cluster_cpp() == 0
+    h.moe_correct_ridge_cpp()
+    read = lambda: (h.get_matrix("Z_corr", np.float64), h.get_matrix("Z_corr", np.float32), h.get_matrix("R", np.float64), h.getZorig())  # noqa: E731
+    one_slab = read()                             # "xfer_slab_bytes" = 0: N cells are one slab of either default
+    h._set("xfer_slab_bytes", XFER_SLAB)          # Z rows: 256 fp64 / 512 fp32 cells per slab; R rows (width K = 16): 128 fp64 cells
+    for got, ref in zip(read(), one_slab):
+        assert got.shape == ref.shape and got.dtype == ref.dtype
+        np.testing.assert_array_equal(got, ref)
+    assert one_slab[2].shape == (XFER_K, N) and np.abs(one_slab[2].sum(axis=0) - 1).max() < 1e-5
+
+
+def test_host_seam_with_full_size_slots():
+    """the default 16 MiB slots: 6 slabs of 16384 cells x 128 fp64 (a last one of 11 cells), so the host threads really split the copies"""
+    N, d = 5 * 16384 + 11, 128
+    skw, want = _xfer_problem(N, np.float64, d=d)
+    h = Harmony(seed=1)
+    h.setup(**skw)
+    assert h.timer("ingest_pinned") == 2
+    back = h.getZorig()
+    np.testing.assert_array_equal(back, want)
+    np.testing.assert_array_equal(back, skw["Z"].astype(np.float32).astype(np.float64))
+    _xfer_memo.pop((N, d, "float64"))             # (84 MB: not kept for the rest of the session)
+
+
+def test_map_query_host_ingest_across_slab_boundaries():
+    from harmony_amd.mapping import prepare_query_args
+    skw, _ = _xfer_problem(2305, np.float64)
+    fit = Harmony(seed=1)
+    fit.setup(**skw)
+    fit.init_cluster_cpp(np.asfortranarray(skw["Z"][:, :XFER_K], dtype=np.float64))
+    assert fit.cluster_cpp() == 0
+    fit.moe_correct_ridge_cpp()
+    ref = fit.reference_summary()
+    Zq, meta, _ = synth(700, d=XFER_D, levels=(3,), seed=11, shard=2)
+    kw, _ = prepare_query_args(Zq, meta, ref, vars_use="cov0")
+    out = []
+    for slab in (0, XFER_SLAB):
+        q = Harmony()
+        q._set("xfer_slab_bytes", slab)
+        q.map_query(**kw)
+        assert q.timer("ingest_pinned") == 2
+        q._set("xfer_slab_bytes", 0)
+        out.append((q.getZorig(), q.getZcorr(), q.getR()))
+    for got, base in zip(out[1], out[0]):
+        np.testing.assert_array_equal(got, base)
+    assert np.array_equal(out[0][0], np.asarray(kw["Zq"], dtype=np.float32).astype(np.float64))
+
+
 def test_update_order_must_be_a_permutation(cell_lines_small):
     from harmony_amd import HarmonyError
     meta = {"dataset": cell_lines_small["dataset_levels"][cell_lines_small["dataset"]]}

@@ -304,6 +304,20 @@ def test_library_checks_the_arguments_before_the_device():
     assert call(handle=None) == HMX_ERR_ARG
 
 
+def test_xfer_slab_bytes_is_a_lab_field_with_the_same_conventions():
+    """the cap on a staging slab of the host matrix seam (hmx_setup / hmx_map_query / hmx_get_matrix with host buffers): 0 is the default"""
+    lib = _lib.load()
+    h = C.c_void_p(lib.hmx_create())
+    try:
+        assert lib.hmx_set_int(h, b"xfer_slab_bytes", -1) == HMX_ERR_ARG
+        assert b"xfer_slab_bytes" in lib.hmx_last_error(h)
+        assert lib.hmx_set_int(h, b"xfer_slab_bytes", 4096) == 0 and lib.hmx_set_int(h, b"xfer_slab_bytes", 0) == 0
+    finally:
+        lib.hmx_destroy(h)
+    lab = open(os.path.join(ROOT, "include", "harmony_mi355x_lab.h")).read()
+    assert '"xfer_slab_bytes"' in lab
+
+
 @pytest.mark.skipif(not NO_GPU, reason="a GPU is present")
 def test_no_cpu_fallback():
     c = pr.random_case(6, 12, 8, 3, seed=2)

@@ -178,6 +178,12 @@ int64_t hmx_get(hmx_ctx* ctx, const char* field, double* out, int64_t cap) {
   if (f == "snn:long_rows") return scalar((double)ctx->snn_long_rows);      // ... and the rows that took the windowed path
   if (f == "snn:short_cap") return scalar((double)SNN_SHORT_CAP);      // the largest candidate count one wave sorts in LDS; the cells of the long path's window
   if (f == "snn:window") return scalar((double)SNN_WINDOW);
+  if (f == "louvain:levels") return scalar((double)ctx->louvain_levels);      // the last hmx_louvain: recorded levels, the level returned (0: the singletons), sweeps of all levels, clusters
+  if (f == "louvain:best_level") return scalar((double)ctx->louvain_best_level);
+  if (f == "louvain:sweeps") return scalar((double)ctx->louvain_sweeps);
+  if (f == "louvain:clusters") return scalar((double)ctx->louvain_clusters);
+  if (f == "louvain:long_rows") return scalar((double)ctx->louvain_long_rows);      // ... and the rows of level 0 above the short path's cap
+  if (f == "louvain:short_cap") return scalar((double)(ctx->louvain_short_cap >= 0 ? std::min<int64_t>(ctx->louvain_short_cap, LV_SHORT_CAP) : LV_SHORT_CAP));
   if (f == "carried_rounds") return scalar((double)ctx->carried_rounds);
   if (f == "rounds_without_R") return scalar((double)ctx->rounds_without_R);
   if (f == "chain_rounds") return scalar((double)ctx->chain_rounds);

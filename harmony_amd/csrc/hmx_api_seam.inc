@@ -188,6 +188,9 @@ struct hmx_ctx {
   int64_t graph_cc_rounds = 0;
   // ---- the SNN graph (hmx_snn_from_knn / hmx_snn_graph): the pruning threshold and the long rows of the last call ("snn:s_min", "snn:long_rows")
   int64_t snn_s_min = 0, snn_long_rows = 0;
+  // ---- Louvain clustering (hmx_louvain): the counters of the last call ("louvain:levels" ...) and the lab field "louvain_short_cap", a cap
+  // below the short path's own on the entries of a row it takes (-1: the default)
+  int64_t louvain_levels = 0, louvain_best_level = 0, louvain_sweeps = 0, louvain_clusters = 0, louvain_long_rows = 0, louvain_short_cap = -1;
   // ---- the reference's PCA (hmx_pca_prepare / apply / release, hmx_api_pca.inc): the prepared lists (a PcaState) and their entry count
   std::shared_ptr<void> pca; int64_t pca_entries = 0;
   QueryDev qd{};            // the query's device tables (rows in D.Zo / D.Zc, internal order in D.perm / D.invperm)

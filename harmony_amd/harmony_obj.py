@@ -330,6 +330,13 @@ class Harmony(object):
         from .snn import harmony_snn
         return harmony_snn(self, k, prune)
 
+    def clusters(self, k=20, prune=1.0 / 15.0, resolution=0.8):
+        """Seurat's FindNeighbors and FindClusters on the handle's current Z_corr: the SNN graph (snn) and its Louvain clusters
+        (louvain.louvain) at `resolution`; the defaults are Seurat's.  Returns (labels, n_clusters, modularity, levels), labels in the order
+        the cells were given in, 0 the largest cluster."""
+        from .louvain import harmony_clusters
+        return harmony_clusters(self, k, prune, resolution)
+
     def silhouette(self, meta_data, label_col, group_col=None, return_ab=False):
         """Silhouette widths (silhouette.silhouette_samples) of the handle's current Z_corr over the column `label_col` of meta_data, within the
         levels of `group_col` when one is named; one label per cell in the order the cells were given in.  Returns s, or (s, a, b).  Z_corr

@@ -258,6 +258,28 @@ if sn:
 else:
     vals["SNN_MEASURED"] = "**Not measured yet**: `profiles/snn_bench.json` (written by `tools/snn_bench.py` on an MI355X) is not in the tree."
     vals["SNN_KERNELS"] = "not traced yet"
+lv = line("louvain_bench.json")      # tools/louvain_bench.py
+if lv:
+    cpu = (" networkx's `louvain_communities` on that machine's CPU (one thread) on the same graph: %.1f s, %.0f times as long, %d clusters at Q %.5f."
+           % (lv["cpu_networkx_ms"] / 1e3, lv["cpu_networkx_ms"] / lv["louvain_ms"], lv["cpu_clusters"], lv["cpu_modularity"])) if "cpu_networkx_ms" in lv \
+        else " No one-thread CPU Louvain beside it: %s." % lv.get("cpu_skipped", "not run")
+    vals["LOUVAIN_MEASURED"] = ("**Measured** (`profiles/louvain_bench.json`, one MI355X, the SNN graph of %s cells x %d PCs at k = %d, %s entries, resolution %.1f, "
+                                "`\"timer:louvain\"` alone, median of %d calls): %.0f ms (spread %.1f %%) for %d levels and %d sweeps: %s clusters per level, Q %s, "
+                                "%d clusters at Q %.5f returned (level %d); %d rows on the long path at level 0; the same bits in every call: %s. The CSR crosses the "
+                                "host: %.0f MB in, %.0f ms at 50 GB/s, which a graph kept in HBM after `hmx_snn_graph` would save.%s"
+                                % ("{:,}".format(lv["cells"]).replace(",", " "), lv["d"], lv["k"], "{:,}".format(lv["entries"]).replace(",", " "), lv["resolution"],
+                                   len(lv["louvain_ms_all"]), lv["louvain_ms"], 100.0 * lv["louvain_spread"], lv["levels"], lv["sweeps"],
+                                   " → ".join(str(c) for c in lv["level_clusters"]), " → ".join("%.4f" % q for q in lv["level_modularity"]), lv["clusters"],
+                                   lv["modularity"], lv["best_level"], lv["long_rows"], "yes" if lv["same_bits_every_call"] else "NO", lv["csr_bytes"] / 1e6,
+                                   lv["upload_ms_at_50GBs"], cpu))
+    sm = line("louvain_bench_100k.json")      # the same tool at --cells 100000, where networkx holds the graph
+    if sm and "cpu_networkx_ms" in sm:
+        vals["LOUVAIN_MEASURED"] += (" At %s cells (`profiles/louvain_bench_100k.json`, %s entries) the library takes %.0f ms for %d clusters at Q %.5f; networkx's "
+                                     "`louvain_communities(seed=0)` on one thread of that machine's CPU takes %.1f s, %.0f times as long, for %d clusters at Q %.5f."
+                                     % ("{:,}".format(sm["cells"]).replace(",", " "), "{:,}".format(sm["entries"]).replace(",", " "), sm["louvain_ms"], sm["clusters"],
+                                        sm["modularity"], sm["cpu_networkx_ms"] / 1e3, sm["cpu_networkx_ms"] / sm["louvain_ms"], sm["cpu_clusters"], sm["cpu_modularity"]))
+else:
+    vals["LOUVAIN_MEASURED"] = "**Not measured yet**: `profiles/louvain_bench.json` (written by `tools/louvain_bench.py` on an MI355X) is not in the tree."
 parts = sorted(f for f in os.listdir(os.path.join(ROOT, "docs", "design_parts")) if f.endswith(".md"))
 out = io.StringIO()
 for f in parts:

@@ -17,6 +17,7 @@ from .rank_sums import rank_sums_by_group, wilcoxon_from_rank_sums
 from .silhouette import silhouette_batch, silhouette_label, silhouette_samples
 from .snn import snn, snn_from_knn
 from .ui import RunHarmony, prepare_setup_args
+from .umap import find_ab_params, umap, umap_layout
 from .utils import harmonize
 
 __all__ = ["RunHarmony", "harmony_options", "Harmony", "HarmonyError", "harmonize", "prepare_setup_args", "map_query",
@@ -24,4 +25,4 @@ __all__ = ["RunHarmony", "harmony_options", "Harmony", "HarmonyError", "harmoniz
            "silhouette_samples", "silhouette_label", "silhouette_batch", "HarmonyLoadings", "project_query", "map_query_counts", "gene_stats", "fit_loadings",
            "gene_stats_by_group", "variable_genes", "rank_genes_groups", "markers_from_sums",
            "rank_sums_by_group", "wilcoxon_from_rank_sums", "neighbors", "graph_from_knn", "connected_components", "graph_connectivity",
-           "snn", "snn_from_knn", "louvain"]
+           "snn", "snn_from_knn", "louvain", "umap", "umap_layout", "find_ab_params"]

@@ -184,6 +184,10 @@ int64_t hmx_get(hmx_ctx* ctx, const char* field, double* out, int64_t cap) {
   if (f == "louvain:clusters") return scalar((double)ctx->louvain_clusters);
   if (f == "louvain:long_rows") return scalar((double)ctx->louvain_long_rows);      // ... and the rows of level 0 above the short path's cap
   if (f == "louvain:short_cap") return scalar((double)(ctx->louvain_short_cap >= 0 ? std::min<int64_t>(ctx->louvain_short_cap, LV_SHORT_CAP) : LV_SHORT_CAP));
+  if (f == "umap:fired") return scalar((double)ctx->umap_fired);      // the last hmx_umap_layout: directed firings of its epochs, the epochs run, the rows above the short path's cap
+  if (f == "umap:epochs") return scalar((double)ctx->umap_epochs);
+  if (f == "umap:long_rows") return scalar((double)ctx->umap_long_rows);
+  if (f == "umap:short_cap") return scalar((double)(ctx->umap_short_cap >= 0 ? ctx->umap_short_cap : UM_SHORT_CAP));
   if (f == "carried_rounds") return scalar((double)ctx->carried_rounds);
   if (f == "rounds_without_R") return scalar((double)ctx->rounds_without_R);
   if (f == "chain_rounds") return scalar((double)ctx->chain_rounds);

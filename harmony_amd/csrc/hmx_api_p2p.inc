@@ -167,6 +167,7 @@ int hmx_set_int(hmx_ctx* ctx, const char* field, int64_t v) {
   else if (f == "xfer_slab_bytes") { if (v < 0) return fail(ctx, HMX_ERR_ARG, "xfer_slab_bytes: 0 (the default) or a positive byte count"); ctx->xfer_slab_bytes = v; }
   else if (f == "ranksum_list_bytes") { if (v < 0) return fail(ctx, HMX_ERR_ARG, "ranksum_list_bytes: 0 (the default) or a positive byte count"); ctx->ranksum_list_bytes = v; }
   else if (f == "louvain_short_cap") { if (v < -1) return fail(ctx, HMX_ERR_ARG, "louvain_short_cap: -1 (the default) or an entry count"); ctx->louvain_short_cap = v; }
+  else if (f == "umap_short_cap") { if (v < -1 || v > 2147483647ll) return fail(ctx, HMX_ERR_ARG, "umap_short_cap: -1 (the default) or an entry count"); ctx->umap_short_cap = v; }
   else if (f == "device") ctx->device = (int)v;
   else if (f == "profile") { ctx->profile = (int)(v < 0 ? 0 : v > 2 ? 2 : v); ctx->prof_update_ms = 0; ctx->prof_update_launches = 0; ctx->prof_update_cells = 0; ctx->prof_update_steps = 0; ctx->ev_used = 0;
                              ctx->ph_used = 0; ctx->gpu_timers.clear(); }

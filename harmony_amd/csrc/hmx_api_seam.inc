@@ -191,6 +191,9 @@ struct hmx_ctx {
   // ---- Louvain clustering (hmx_louvain): the counters of the last call ("louvain:levels" ...) and the lab field "louvain_short_cap", a cap
   // below the short path's own on the entries of a row it takes (-1: the default)
   int64_t louvain_levels = 0, louvain_best_level = 0, louvain_sweeps = 0, louvain_clusters = 0, louvain_long_rows = 0, louvain_short_cap = -1;
+  // ---- the UMAP layout (hmx_umap_layout): the counters of the last call ("umap:fired" ...) and the lab field "umap_short_cap", the entries of
+  // a row the one-wave path takes in place of its own cap (-1: the default)
+  int64_t umap_fired = 0, umap_epochs = 0, umap_long_rows = 0, umap_short_cap = -1;
   // ---- the reference's PCA (hmx_pca_prepare / apply / release, hmx_api_pca.inc): the prepared lists (a PcaState) and their entry count
   std::shared_ptr<void> pca; int64_t pca_entries = 0;
   QueryDev qd{};            // the query's device tables (rows in D.Zo / D.Zc, internal order in D.perm / D.invperm)

@@ -337,6 +337,13 @@ class Harmony(object):
         from .louvain import harmony_clusters
         return harmony_clusters(self, k, prune, resolution)
 
+    def umap(self, n_neighbors=15, min_dist=0.5, **kwargs):
+        """The UMAP layout (umap.umap) of the handle's current Z_corr: its neighbour graph (neighbors) laid out from the top principal axes;
+        further arguments (init, n_components, n_epochs, spread, a, b, gamma, learning_rate, negative_sample_rate, seed) as umap.umap takes
+        them.  Returns float32 positions [N, n_components] in the order the cells were given in; two calls give identical coordinates."""
+        from .umap import harmony_umap
+        return harmony_umap(self, n_neighbors, min_dist, **kwargs)
+
     def silhouette(self, meta_data, label_col, group_col=None, return_ab=False):
         """Silhouette widths (silhouette.silhouette_samples) of the handle's current Z_corr over the column `label_col` of meta_data, within the
         levels of `group_col` when one is named; one label per cell in the order the cells were given in.  Returns s, or (s, a, b).  Z_corr

@@ -280,6 +280,38 @@ if lv:
                                         sm["modularity"], sm["cpu_networkx_ms"] / 1e3, sm["cpu_networkx_ms"] / sm["louvain_ms"], sm["cpu_clusters"], sm["cpu_modularity"]))
 else:
     vals["LOUVAIN_MEASURED"] = "**Not measured yet**: `profiles/louvain_bench.json` (written by `tools/louvain_bench.py` on an MI355X) is not in the tree."
+um = line("umap_bench.json")      # tools/umap_bench.py
+if um:
+    def um_text(u):
+        return ("%s cells x %d PCs, `neighbors(n_neighbors=%d)`: %s entries, longest row %d, %d epochs from the PCA start, `\"timer:umap\"` alone, median of %d calls: "
+                "**%.0f ms** (spread %.1f %%), of which %.1f ms (%.0f %%) are the upload of the CSR (%.0f MB) and the checks in front of the epochs (a call that asks for "
+                "no epoch); %.3f ms per epoch = %.0f epochs/s; %s firings per epoch gather %.0f MB of positions (%.2f TB/s) beside %.0f MB streamed (%.2f TB/s); %d rows on "
+                "the long path; the same bits in every call: %s; trustworthiness (k = 15) of %d sampled cells %.4f (the PCA start: %.4f), kNN purity by cell type %.4f"
+                % ("{:,}".format(u["cells"]).replace(",", " "), u["d"], u["n_neighbors"], "{:,}".format(u["entries"]).replace(",", " "), u["longest_row"], u["epochs"],
+                   len(u["umap_ms_all"]), u["umap_ms"], 100.0 * u["umap_spread"], u["front_ms"], 100.0 * u["front_share"], u["csr_bytes"] / 1e6, u["epoch_ms"],
+                   u["epochs_per_s"], "{:,}".format(int(u["firings_per_epoch"])).replace(",", " "), u["gather_bytes_per_epoch"] / 1e6, u["gather_TBps"],
+                   u["stream_bytes_per_epoch"] / 1e6, u["stream_TBps"], u["long_rows"], "yes" if u["same_bits_every_call"] else "NO", u["sample"],
+                   u["trustworthiness"], u["trustworthiness_of_start"], u["knn_purity"]))
+    vals["UMAP_MEASURED"] = ("**Measured** (`profiles/umap_bench.json`, one MI355X): " + um_text(um) + ". Against the machine: the gathers are 64-byte lines of an "
+                             "8 MB array that stays in cache, so %.2f TB/s of useful bytes is %.1f TB/s of lines, against about 8.6 TB/s measured for random rows out "
+                             "of the Infinity Cache and 6.3 TB/s achievable from HBM for the streamed part: the epoch is bound by the latency of its dependent loads, "
+                             "not by either rate. No CPU UMAP was raced against it: umap-learn was not installed on that machine, and the pure-Python loop of the "
+                             "spec is no yardstick." % (um["gather_TBps"], um["gather_TBps"] * 64.0 / 8.0))
+    sm = line("umap_bench_100k.json")
+    if sm:
+        vals["UMAP_MEASURED"] += " At " + um_text(sm) + " (`profiles/umap_bench_100k.json`)."
+    try:      # the kernel table of one call at 1M cells (rocprofv3 --kernel-trace --stats, a run of its own)
+        import csv
+        ks = []
+        for row in csv.DictReader(open(os.path.join(P, "umap_kernel_stats.csv"))):
+            name = row["Name"].replace("void ", "").replace("hmx::", "").split("(")[0]
+            if name.startswith(("k_um_", "k_lv_check", "k_cc_check")):
+                ks.append((float(row["AverageNs"]) / 1e6, int(row["Calls"]), name))
+        vals["UMAP_MEASURED"] += " Per kernel (`profiles/umap_kernel_stats.csv`, two calls, one of them for no epoch): " + "; ".join("`%s` %.3f ms x %d" % (n, ms, c) for ms, c, n in sorted(ks, reverse=True)) + "."
+    except Exception:
+        missing.append("umap_kernel_stats.csv")
+else:
+    vals["UMAP_MEASURED"] = "**Not measured yet**: `profiles/umap_bench.json` (written by `tools/umap_bench.py` on an MI355X) is not in the tree."
 parts = sorted(f for f in os.listdir(os.path.join(ROOT, "docs", "design_parts")) if f.endswith(".md"))
 out = io.StringIO()
 for f in parts:

@@ -106,8 +106,11 @@ RcclApi* rccl_api(std::string* err) {
 // Two persistent block chains must never be resident at once: each needs one workgroup on EVERY CU and spins on its peers, so
 // two of them sharing the CUs would starve each other (bounded spins turn that into an error, not a hang -- but the round is
 // lost).  Handles of one process are therefore chained through an event per device: a chain launch waits for the previous
-// chain launch of any handle on that device.  (Two PROCESSES running unsharded chains on one GPU are not protected; HMX_CHAIN=0.)
-struct ChainGate { std::mutex mu; std::map<int, hipEvent_t> last; std::map<int, const void*> owner; };
+// chain launch of any OTHER stream on that device (a stream orders its own launches).  (Two PROCESSES running unsharded chains on one GPU are not protected; HMX_CHAIN=0.)
+struct ChainGate {      // per device (chain_gate_enter / chain_gate_release, hmx_api_update.inc)
+  struct PerDevice { hipEvent_t ev = nullptr; bool owned = false; hipStream_t owner = nullptr; bool armed = false; };      // owned: `owner` (which may be the null stream) made the last chain launch
+  std::mutex mu; std::map<int, PerDevice> dev;
+};
 ChainGate& chain_gate() { static ChainGate g; return g; }
 
 double now_ms() {
@@ -134,6 +137,7 @@ void hmx_destroy(hmx_ctx* ctx) {
   for (int g = 0; g < 8; g++) if (ctx->p2p_peer[g] && ctx->p2p_peer[g] != ctx->p2p_self) (void)hipIpcCloseMemHandle(ctx->p2p_peer[g]);
   if (ctx->p2p_self) (void)hipFree(ctx->p2p_self);
   if (ctx->p2p_result) (void)hipFree(ctx->p2p_result);
+  chain_gate_release(ctx);
   free_all(ctx);
   if (ctx->own_stream && ctx->L.stream) (void)hipStreamDestroy(ctx->L.stream);
   delete ctx;
@@ -245,7 +249,7 @@ int hmx_restart(hmx_ctx* ctx) {
   l_normalize_from(ctx->L, D.Zo, D.Zc, D.n, D.d, D.zs); KCHK();  // Z_corr = normalise(Z_orig) :42 (one pass)
   ctx->ledger.restart();      // (R is rewritten, and no order set is taken for sorted)
   HIPCHK(hipStreamSynchronize(ctx->L.stream));
-  ctx->obj_pending = 0; ctx->obj_harmony_pending = false;
+  ctx->obj_pending = 0; ctx->obj_harmony_pending = false; ctx->obj_unrecorded = false;
   ctx->obj_kmeans.clear(); ctx->obj_dist.clear(); ctx->obj_entropy.clear(); ctx->obj_cross.clear(); ctx->obj_harmony.clear();
   ctx->kmeans_rounds.clear(); ctx->round_counter = 0; ctx->ran_init = false; ctx->injected.clear(); ctx->rrng_seeded = false;
   ctx->y_on_device = false; ctx->solve_pending = false;
@@ -339,6 +343,7 @@ int hmx_cluster(hmx_ctx* ctx) {  // src/harmony.cpp:208-262
       if (check_convergence_impl(ctx, 0)) { iter++; break; }
     }
   }
+  CHK(record_objectives(ctx));      // once per call: hmx_check_convergence then waits for this call's rounds, not for a correction queued behind them
   ctx->kmeans_rounds.push_back(iter);
   ctx->obj_harmony_pending = true;   // objective_harmony <- objective_kmeans.back() (:260), resolved with the pending rounds
   if (ctx->obj_pending == 0) { ctx->obj_harmony.push_back(ctx->obj_kmeans.back()); ctx->obj_harmony_pending = false; }

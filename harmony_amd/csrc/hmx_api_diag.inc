@@ -188,6 +188,9 @@ int64_t hmx_get(hmx_ctx* ctx, const char* field, double* out, int64_t cap) {
   if (f == "umap:epochs") return scalar((double)ctx->umap_epochs);
   if (f == "umap:long_rows") return scalar((double)ctx->umap_long_rows);
   if (f == "umap:short_cap") return scalar((double)(ctx->umap_short_cap >= 0 ? ctx->umap_short_cap : UM_SHORT_CAP));
+  if (f == "diag:launches") return scalar((double)ctx->n_launches);      // since setup: kernel launches of the clustering / correction launchers (hmx_k_launch.inc; copies and memsets are not kernels of ours)
+  if (f == "diag:event_records") return scalar((double)ctx->n_event_records);      // ... and events recorded (objective slots, the chain gate across streams, profile mode's phases)
+  if (f == "diag:gate_records") return scalar((double)ctx->n_gate_records);      // ... those of them that were the chain gate's: they depend on which stream of the PROCESS launched a chain last
   if (f == "carried_rounds") return scalar((double)ctx->carried_rounds);
   if (f == "rounds_without_R") return scalar((double)ctx->rounds_without_R);
   if (f == "chain_rounds") return scalar((double)ctx->chain_rounds);
@@ -200,7 +203,8 @@ int64_t hmx_get(hmx_ctx* ctx, const char* field, double* out, int64_t cap) {
     for (int k = 0; k < 3; k++) if (f.substr(7) == RIDGE_KIND_NAME[k] && ctx->ridge_seen[k]) {
       const RidgeLaunch& t = ctx->last_ridge[k];
       return vec(std::vector<double>{(double)t.valid, (double)t.mfma, (double)t.p0, (double)t.p1, (double)t.gx, (double)t.gy, (double)t.gz, (double)t.threads, (double)t.lds,
-                                     (double)t.lds_b_bytes, (double)t.lds_body_bytes, (double)t.lds_mask_off, (double)t.rgx, (double)t.rgy});
+                                     (double)t.lds_b_bytes, (double)t.lds_body_bytes, (double)t.lds_mask_off, (double)t.rgx, (double)t.rgy,
+                                     (double)t.lds_sys_off, (double)t.lds_total});      // (the solve's systems in LDS: their offset, 0: global scratch; the launch's LDS in all)
     }
     return -1;      // (no such kind, or no launch of it on this handle yet)
   }

@@ -98,6 +98,9 @@ static void p2p_auto(hmx_ctx* ctx, RcclApi* api, int rank, int world) {
 }
 int hmx_set_stream(hmx_ctx* ctx, void* s) {
   if (!ctx) return HMX_ERR_ARG;
+  if ((hipStream_t)s == ctx->L.stream) return 0;
+  if (ctx->obj_unrecorded && ctx->obj_event && ctx->L.stream) { (void)hipEventRecord(ctx->obj_event, ctx->L.stream); ctx->n_event_records++; ctx->obj_unrecorded = false; }      // (the slots were written on the old stream)
+  chain_gate_release(ctx);
   if (ctx->own_stream && ctx->L.stream) (void)hipStreamDestroy(ctx->L.stream);
   ctx->L.stream = (hipStream_t)s; ctx->own_stream = false;
   return 0;

@@ -170,7 +170,10 @@ int ridge_ran(hmx_ctx* ctx, RidgeKind kind, const RidgeLaunch& t) {
 int ridge_statistics(hmx_ctx* ctx) {
   const Dev& D = ctx->D;
   PhaseScope ph(ctx, "ridge_statistics");
-  l_zero4(ctx->L, D.Sq, (size_t)D.Q * D.d * D.K, D.nq, (size_t)D.Q * D.K, nullptr, 0, nullptr, 0); KCHK();      // (one launch instead of two memsets)
+  // the slot form overwrites every entry of Sq and nq with plain stores (k_moe_stats_reduce): only the first-generation kernels' atomics and the
+  // sequential sums start from zero
+  const bool slot_form = ctx->ridge_arith != 1 && D.moe_mfma && D.st_dma;
+  if (!slot_form) { l_zero4(ctx->L, D.Sq, (size_t)D.Q * D.d * D.K, D.nq, (size_t)D.Q * D.K, nullptr, 0, nullptr, 0); KCHK(); }      // (one launch instead of two memsets)
   if (ctx->ridge_arith == 1) CHK(seq_ridge_stats(ctx));
   else { CHK(ridge_ran(ctx, RidgeKind::Stats, l_moe_stats(ctx->L, D))); KCHK(); }
   CHK(allreduce(ctx, D.Sq, (int64_t)D.Q * D.d * D.K, 1));
@@ -189,6 +192,7 @@ int ridge_device_tail(hmx_ctx* ctx) {
   A.Of = ctx->oe_arith ? ctx->Of : nullptr; A.Ef = ctx->oe_arith ? ctx->Ef : nullptr; A.solve_f32 = ctx->solve_arith;
   A.ref_tot = (seq && ctx->C > 1) ? ctx->rg_tot : nullptr; A.pair_tot = ctx->rp_tot; A.pair_idx = ctx->pair_idx;
   A.lds_b_bytes = s.lds_b_bytes; A.lds_body_bytes = s.lds_body_bytes; A.lds_mask_off = s.lds_mask_off;
+  A.lds_sys_off = s.lds_sys_off;
   { PhaseScope ph(ctx, "arma_inv"); CHK(ridge_ran(ctx, RidgeKind::Solve, l_moe_solve(ctx->L, D, A))); KCHK(); }
   { PhaseScope ph(ctx, "update_Zcorr"); CHK(ridge_ran(ctx, RidgeKind::Apply, l_moe_apply(ctx->L, D))); KCHK(); }
   ctx->y_on_device = true; ctx->solve_pending = true;

@@ -65,6 +65,10 @@ struct hmx_ctx {
   // objective snapshots are read back asynchronously: one pinned 3-double slot per clustering round, resolved into the
   // four series when a value is needed (convergence checks, getters) -- no host sync per round
   double* h_obj = nullptr; int obj_cap = 0, obj_pending = 0; hipEvent_t obj_event = nullptr; bool obj_harmony_pending = false;
+  // obj_unrecorded: a round has written its slot from inside its closing launch and obj_event has not been recorded behind it yet -- recorded once at the
+  // end of hmx_cluster, or by flush_objectives when a value is needed earlier (an event record is a barrier packet between two dependent launches)
+  bool obj_unrecorded = false;
+  long long n_launches = 0, n_event_records = 0, n_gate_records = 0;      // since setup: kernel launches of the launchers (Launch::count) / events the library recorded / those of them that were the chain gate's ("diag:launches", "diag:event_records", "diag:gate_records")
   // randomness: 0 = documented counter-based generator, 1 = R-compatible (MT19937 seeded like set.seed, arma draw order)
   int rng_mode = 0; hmx::RRng rrng; bool rrng_seeded = false;
   // device-side ridge solve (default; HMX_MOE_SOLVE=host selects the synchronous host path): scratch and result buffers
@@ -242,7 +246,7 @@ void free_all(hmx_ctx* ctx) {
   }
   if (ctx->h_obj) { (void)hipHostFree(ctx->h_obj); ctx->h_obj = nullptr; ctx->obj_cap = 0; }
   if (ctx->obj_event) { (void)hipEventDestroy(ctx->obj_event); ctx->obj_event = nullptr; }
-  ctx->obj_pending = 0; ctx->obj_harmony_pending = false;
+  ctx->obj_pending = 0; ctx->obj_harmony_pending = false; ctx->obj_unrecorded = false;
 }
 template <class T> int h2d(hmx_ctx* ctx, T* dst, const T* src, size_t count) {
   if (count) HIPCHK(hipMemcpyAsync(dst, src, count * sizeof(T), hipMemcpyHostToDevice, ctx->L.stream));
@@ -320,9 +324,9 @@ struct PhaseScope {
     }
     idx = (int)c->ph_used++;
     c->ph_pool[idx].name = id;
-    (void)hipEventRecord(c->ph_pool[idx].a, c->L.stream);
+    (void)hipEventRecord(c->ph_pool[idx].a, c->L.stream); c->n_event_records++;
   }
-  ~PhaseScope() { if (idx >= 0) (void)hipEventRecord(c->ph_pool[idx].b, c->L.stream); }
+  ~PhaseScope() { if (idx >= 0) { (void)hipEventRecord(c->ph_pool[idx].b, c->L.stream); c->n_event_records++; } }
 };
 // profile mode: the dominant kernel's launches carry their own start / stop events (hipExtLaunchKernelGGL: the timestamps of the dispatch
 // packet itself, no barrier packets around it)
@@ -360,8 +364,15 @@ int upload_Y(hmx_ctx* ctx) {  // host Y[k*d+j] -> device Ycur, from it (k_y_imag
 
 // objective snapshot obj[2..4] -> the four series (src/harmony.cpp:165-168).  The copy is enqueued into a pinned slot;
 // flush_objectives() waits for the last copy only (an event, not the stream: later kernels keep running) and appends.
+int record_objectives(hmx_ctx* ctx) {      // obj_event behind every slot written so far
+  if (!ctx->obj_unrecorded) return 0;
+  HIPCHK(hipEventRecord(ctx->obj_event, ctx->L.stream)); ctx->n_event_records++;
+  ctx->obj_unrecorded = false;
+  return 0;
+}
 int flush_objectives(hmx_ctx* ctx) {
   if (!ctx->obj_pending) return 0;
+  CHK(record_objectives(ctx));
   HIPCHK(hipEventSynchronize(ctx->obj_event));
   const float norm_const = 2000 / ((float)ctx->N_global);
   for (int i = 0; i < ctx->obj_pending; i++) {
@@ -399,7 +410,8 @@ int push_objective(hmx_ctx* ctx) {
   double* slot = nullptr;
   CHK(objective_slot(ctx, &slot));
   HIPCHK(hipMemcpyAsync(slot, ctx->D.obj + 2, sizeof(double) * 4, hipMemcpyDeviceToHost, ctx->L.stream));   // dist, entropy, cross, chain error word
-  HIPCHK(hipEventRecord(ctx->obj_event, ctx->L.stream));
+  HIPCHK(hipEventRecord(ctx->obj_event, ctx->L.stream)); ctx->n_event_records++;
+  ctx->obj_unrecorded = false;      // (the stream orders the earlier slots in front of this one)
   ctx->obj_pending++;
   return 0;
 }
@@ -413,6 +425,7 @@ int head_pass(hmx_ctx* ctx, bool normalise = false) {   // normalise: Z_corr <- 
   in.carry_ok = ctx->carry_ok; in.host_order = !ctx->injected.empty() || ctx->rng_mode != 0; in.normalise = normalise;
   in.NT4 = ctx->D.NT4; in.NCT = ctx->D.NCT; in.upd_wps = ctx->D.upd_wps; in.max_iter_kmeans = ctx->max_iter_kmeans;
   in.poll = ctx->poll != nullptr; in.r_store_always = ctx->r_store_always; in.seed = ctx->seed; in.round = (int64_t)ctx->round_counter;
+  in.sharded = ctx->world > 1 || ctx->comm_force; in.ref_arith = ctx->oe_arith || ctx->obj_arith;
   if (head_gathers(in)) {
     PhaseScope ph(ctx, "randomize");
     CHK(prepare_round(ctx, ctx->round_counter));     // (update_R finds this round sorted)
@@ -429,13 +442,18 @@ int head_pass(hmx_ctx* ctx, bool normalise = false) {   // normalise: Z_corr <- 
   const size_t n_sold = hp.clear_first ? (size_t)D.nb * D.B * D.K : 0;
   if (hp.files) ctx->ledger.head_filed(in.round, in.seed);
   ctx->R_valid = false;
-  // O, the contribution replicas, the objective slots (and a stale old-contribution table): ONE launch instead of three or four memsets
-  l_zero4(ctx->L, D.O_fx, (size_t)D.B * D.K, D.Snew_fx, (size_t)D.nrep * D.B * D.K, D.objpart, 2 * (size_t)D.objslots * D.nwmax, zero_sold, n_sold); KCHK();
+  // O, the contribution replicas, the objective slots (and a stale old-contribution table): ONE launch instead of three or four memsets -- of
+  // those the plan still asks for (l_zero4 launches nothing when there is nothing to clear)
+  l_zero4(ctx->L, D.O_fx, hp.clear_O ? (size_t)D.B * D.K : 0, D.Snew_fx, hp.clear_set ? (size_t)D.nrep * D.B * D.K : 0,
+          D.objpart, hp.clear_objpart ? 2 * (size_t)D.objslots * D.nwmax : 0, zero_sold, n_sold); KCHK();
+  D.head_noobj = hp.skip_obj ? 1 : 0;
+  ctx->ledger.head_started();
   CHK(tile_ran(ctx, TileKind::Head, l_tile_static(ctx->L, D, TileKind::Head))); KCHK();      // MFMA tiles; O contributions land in the Snew replicas
-  l_fold(ctx->L, D, -1, 0); KCHK();         // O = sum of the replicas
-  l_obj_reduce(ctx->L, D); KCHK();
+  l_fold(ctx->L, D, -1, hp.clear_O ? 0 : 3); KCHK();         // O = sum of the replicas
+  ctx->ledger.head_folded();
+  if (!hp.skip_obj) { l_obj_reduce(ctx->L, D); KCHK(); }
   CHK(allreduce(ctx, D.O_fx, (int64_t)D.B * D.K, 0));
-  CHK(allreduce(ctx, D.obj, 2, 1));
+  if (!hp.skip_obj) CHK(allreduce(ctx, D.obj, 2, 1));
   if (ctx->oe_arith) CHK(oe_head(ctx));        // E = sum(R, 1) Pr_b^T, O = R Phi^T as the reference sums them (:149-150)
   ctx->R_valid = D.r_store != 0;
   return 0;

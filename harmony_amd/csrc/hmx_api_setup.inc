@@ -169,6 +169,8 @@ static int plan_device(hmx_ctx* ctx, const Design& G, Plan& P) {
   D.st_KH = P.st_KH; D.st_halves = P.st_halves; D.st_dma = P.st_dma; D.st_cpw = P.st_cpw; D.st_nwg = P.st_nwg;
   D.chain_pair = P.chain_pair; D.KH = P.KH; D.chain_folders = P.chain_folders; D.chain_kw = P.chain_kw;
   D.r_store = 1;
+  D.solve_lds = (!sw.solve_lds_off && !S.sharded && P.solve_on_device && !ctx->ridge_arith && !ctx->solve_arith) ? 1 : 0;
+  ctx->n_launches = ctx->n_event_records = ctx->n_gate_records = 0; ctx->L.count = &ctx->n_launches;
   D.chain_wps = 2;      // (the 3- / 4-waves-per-SIMD chain variants and the in-chain gathering of the old contributions lost rounds 2 and 3: removed in round 5)
   D.nchunks = (int)G.schunks.size(); D.nitems = (int)G.items.size(); D.naitems = (int)G.aitems.size(); D.ntitems = (int)G.titems.size();
   D.p2p_world = 0; D.p2p_rank = ctx->p2p_rank;

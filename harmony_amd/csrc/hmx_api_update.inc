@@ -1,4 +1,40 @@
 // hmx_api_update.inc -- part of hmx_api.cpp (included there, ONE translation unit): update_R: the rounds of a cluster_cpp call (chain / launch-per-step, carry, R-store elision)
+// ---- the chain gate (ChainGate, hmx_api.cpp): the stream of the last chain launch OWNS the device's gate; its own launches are ordered by the stream, with
+// no event at all.  A launch from another stream records the gate's event on the owner's stream -- under the gate's mutex, so behind the owner's last chain
+// launch -- and waits for it: the exclusion between two handles' persistent launches is what an event per launch gave.  An owner that goes away (hmx_destroy,
+// hmx_set_stream) records once and leaves the event armed for whoever launches next.  A caller's stream must therefore outlive its handle (or be replaced through
+// hmx_set_stream first); if the record on an owner's stream fails all the same, ownership is dropped and the launch waits for the whole device instead.
+int chain_gate_enter(hmx_ctx* ctx, ChainGate& gate) {      // gate.mu held
+  ChainGate::PerDevice& g = gate.dev[ctx->device];
+  const bool mine = g.owned && g.owner == ctx->L.stream;
+  if (g.owned && !mine) {
+    hipError_t e = g.ev ? hipSuccess : hipEventCreateWithFlags(&g.ev, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventRecord(g.ev, g.owner);
+    g.owned = false; g.owner = nullptr;
+    if (e == hipSuccess) { ctx->n_event_records++; ctx->n_gate_records++; g.armed = true; }
+    else {      // the owner's stream is gone (a caller's stream destroyed without hmx_set_stream): nothing can be recorded behind its launches -- wait for the device
+      (void)hipGetLastError(); g.armed = false;
+      HIPCHK(hipDeviceSynchronize());
+    }
+  }
+  if (g.armed && !mine) HIPCHK(hipStreamWaitEvent(ctx->L.stream, g.ev, 0));
+  g.armed = false;
+  return 0;
+}
+void chain_gate_own(hmx_ctx* ctx, ChainGate& gate) { ChainGate::PerDevice& g = gate.dev[ctx->device]; g.owned = true; g.owner = ctx->L.stream; }      // gate.mu held, behind the launch
+void chain_gate_release(hmx_ctx* ctx) {      // the handle's stream is about to go away (or to be replaced)
+  if (ctx->device < 0) return;
+  ChainGate& gate = chain_gate();
+  std::lock_guard<std::mutex> lk(gate.mu);
+  auto it = gate.dev.find(ctx->device);
+  if (it == gate.dev.end() || !it->second.owned || it->second.owner != ctx->L.stream) return;
+  ChainGate::PerDevice& g = it->second;
+  (void)hipSetDevice(ctx->device);
+  if (!g.ev && hipEventCreateWithFlags(&g.ev, hipEventDisableTiming) != hipSuccess) g.ev = nullptr;
+  if (g.ev && hipEventRecord(g.ev, ctx->L.stream) == hipSuccess) { ctx->n_event_records++; ctx->n_gate_records++; g.armed = true; }
+  else { (void)hipGetLastError(); (void)hipStreamSynchronize(ctx->L.stream); }      // (no event: the launches end before the stream goes)
+  g.owned = false; g.owner = nullptr;
+}
 // ---- update_R (src/harmony.cpp:269-342) ---------------------------------------------------------
 int update_R(hmx_ctx* ctx) {
   if (ctx->oe_arith) return update_R_ref(ctx);
@@ -31,6 +67,7 @@ int update_R(hmx_ctx* ctx) {
       l_oldsum(ctx->L, D); KCHK();
     }
     lg.round_started();
+    if (rp.path == PATH_STEP_LOOP) lg.step_loop_used();
     if (rp.reduce_old) CHK(allreduce(ctx, D.Sold_fx, (int64_t)nSold, 0));      // (p2p chain: the folder exchanges new(j - 1) - old_local(j), the ranks' old sums meet there)
     if (rp.clear_next) HIPCHK(hipMemsetAsync(D.Sold_next, 0, sizeof(long long) * nSold, ctx->L.stream));
     if (rp.write_next) lg.round_filed_next(rnd, ctx->seed);
@@ -51,13 +88,9 @@ int update_R(hmx_ctx* ctx) {
     {
       ChainGate& gate = chain_gate();
       std::lock_guard<std::mutex> lk(gate.mu);
-      hipEvent_t& ev = gate.last[ctx->device];
-      const void*& owner = gate.owner[ctx->device];
-      if (!ev) HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-      else if (owner != (const void*)ctx->L.stream) HIPCHK(hipStreamWaitEvent(ctx->L.stream, ev, 0));   // (the same stream orders its own launches: no event, ~20 us of barrier packet less per round)
+      CHK(chain_gate_enter(ctx, gate));      // (the same stream orders its own launches: no event recorded, none waited for)
       { Launch Le; CHK(launch_with_events(ctx, Le)); CHK(tile_ran(ctx, TileKind::Chain, l_chain(Le, D, ctx->chain_wgs))); KCHK(); }
-      HIPCHK(hipEventRecord(ev, ctx->L.stream));
-      owner = (const void*)ctx->L.stream;
+      chain_gate_own(ctx, gate);
     }
     if (ctx->profile) ctx->prof_update_steps += D.nb;
     ctx->chain_check = true;
@@ -115,7 +148,7 @@ int update_R(hmx_ctx* ctx) {
       l_round_tail(ctx->L, D, slot, D.Sold_fx, 0, D.Snew_set[0], 0); KCHK();
     } else if (rp.close == CLOSE_TAIL) { l_round_tail(ctx->L, D, slot, D.Sold_fx, nSold, D.Snew_set[0], nSets); KCHK(); }
     lg.tail_cleared();
-    HIPCHK(hipEventRecord(ctx->obj_event, ctx->L.stream));
+    ctx->obj_unrecorded = true;      // (obj_event: once at the end of hmx_cluster, or in front of a flush that is really taken -- record_objectives)
     ctx->obj_pending++;
   }
   lg.flip();      // next round subtracts what this round's tile kernels collected (or a fresh k_oldsum pass)

@@ -172,6 +172,8 @@ struct Dev {
   int usig;         // all clusters share one sigma (scalar-constant kernel variants)
   unsigned long long* lcnt;  // [K]
   float* ynorm;     // [K]
+  int head_noobj;   // k_tile MODE 1 leaves no objective partials: the head of a cluster_cpp call whose first round's close overwrites obj[0..1] unread (plan_head: skip_obj)
+  int solve_lds;    // k_moe_solve keeps its systems (cov, rhs) in LDS where they fit behind its other LDS (plan_ridge_launch): exact arithmetic on one GPU, HMX_SOLVE_LDS != 0
 };
 
 // arguments of the device-side ridge solve (k_moe_solve)
@@ -190,12 +192,14 @@ struct SolveArgs {
   size_t lds_b_bytes;              // LDS bytes available for the right-hand sides during the substitution (0: leave them in HBM)
   size_t lds_body_bytes;           // LDS bytes behind the index arrays (panel / right-hand sides; the combination-row table during the assembly)
   size_t lds_mask_off;             // byte offset of the coupling masks behind them (0: none -- dense Schur complement)
+  size_t lds_sys_off;              // byte offset of cov [M*M] and rhs [d*M] in LDS behind everything else (0: the global scratch above)
 };
 
 struct Launch {
   hipStream_t stream;
   int grid;  // workgroups for streaming kernels
   hipEvent_t ev0 = nullptr, ev1 = nullptr;   // l_update / l_chain: start / stop events attached to the launch itself (profile mode)
+  long long* count = nullptr;                // the handle's tally of kernel launches (hmx_get "diag:launches"); nullptr: nobody counts
 };
 
 // ---- launchers (hmx_kernels.hip) -----------------------------------------------------

@@ -315,7 +315,11 @@ __device__ __forceinline__ size_t yimg_index(const Dev& D, int j, int k) {
 //   host solve path, HMX_MOE_SOLVE=host, retries with LU) --, W = cov^-1 rhs, Y[:,k] = W[0,:], W[0,:] = 0 (:610-611), correction table Wq[q][k][:] = sum of the kept
 //   levels' rows of combination q (+ its MFMA image), Y <- normalise (:633).
 // flags[k]: bit 0 subset path, bit 1 skipped (no covariate with two kept levels), bit 2 singular system.
-__global__ __launch_bounds__(1024) void k_moe_solve(Dev D, SolveArgs A) {
+// SYSLDS: cov and rhs live in LDS behind the rest (A.lds_sys_off) instead of the global scratch: the ~20 workgroup barriers of a solve then separate LDS accesses,
+// not global round trips.  Same operations in the same order either way.
+// (two kernels over one body, k_moe_solve: global scratch, k_moe_solve_lds: SYSLDS)
+template <bool SYSLDS>
+__device__ __forceinline__ void moe_solve_body(const Dev& D, const SolveArgs& A) {
   extern __shared__ int sm_[];
   const int K = D.K, B = D.B, C = D.C, d = D.d, Q = D.Q, M = B + 1;
   const int k = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
@@ -326,8 +330,9 @@ __global__ __launch_bounds__(1024) void k_moe_solve(Dev D, SolveArgs A) {
   int* prow = sm_ + 3 * B + 4 + C;   // [B + 1] design row (reference order: intercept, kept levels ascending) -> row of the system as it is solved
   const int PAN_OFF = (4 * B + 6 + C) & ~1;      // ints in front of the fp64 panel space
   __shared__ int sch_nd;             // levels of the covariate whose (diagonal) block is eliminated first, 0: none
-  double* cov = A.cov + (size_t)k * M * M;
-  double* rhs = A.rhs + (size_t)k * d * M;
+  double* cov; double* rhs;
+  if constexpr (SYSLDS) { cov = reinterpret_cast<double*>(reinterpret_cast<char*>(sm_) + A.lds_sys_off); rhs = cov + (size_t)M * M; }
+  else { cov = A.cov + (size_t)k * M * M; rhs = A.rhs + (size_t)k * d * M; }
   for (int b = tid; b < B; b += nt) {
     const float o = A.Of ? A.Of[(size_t)b * K + k] : (float)((double)D.O_fx[(size_t)b * K + k] * FX_INV);
     okb[b] = (o / D.sizes[b]) > A.cutoff ? 1 : 0;
@@ -782,6 +787,8 @@ __global__ __launch_bounds__(1024) void k_moe_solve(Dev D, SolveArgs A) {
     bfimg_store_all(D, j, k, y);
   }
 }
+__global__ __launch_bounds__(1024) void k_moe_solve(Dev D, SolveArgs A) { moe_solve_body<false>(D, A); }
+__global__ __launch_bounds__(1024) void k_moe_solve_lds(Dev D, SolveArgs A) { moe_solve_body<true>(D, A); }
 
 // ---- MFMA variants of the two MoE passes (static 16-cell tiles, rows of a tile are contiguous in HBM) ----
 // k_moe_stats_q: Sq[q] (K x d) += R_tile^T (K x 16) * Zo_tile (16 x d): the 16 cells are the MFMA reduction dim.  A workgroup streams a contiguous range of tiles; its

@@ -634,7 +634,8 @@ __global__ __launch_bounds__(1024) void k_oldsum_stream4(Dev D) {
 // Phase 1 (k_fold): O_fx[b][k] += Snew - Sold[j]; Snew = 0.   Phase 2 (k_penalty): pen[b][k].
 // One thread per table entry; two launches because phase 2 reads a column sum of phase 1.
 // mode 0: O += sum_rep Snew[rep] - Sold[j] (single GPU).  mode 1: Snew[0] = sum_rep Snew[rep] only (the
-// sharded path all-reduces Snew[0] next).  mode 2: O += Snew[0] - Sold[j] (after that all-reduce).
+// sharded path all-reduces Snew[0] next).  mode 2: O += Snew[0] - Sold[j] (after that all-reduce).  mode 3: O = sum_rep Snew[rep] -- the head's
+// fold: O is written, never read, so nobody has to clear it first.
 __global__ void k_fold(Dev D, int j, int mode) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   const int n = D.B * D.K;
@@ -642,7 +643,7 @@ __global__ void k_fold(Dev D, int j, int mode) {
   long long sn = D.Snew_fx[i];
   if (mode != 2) for (int r = 1; r < D.nrep; r++) { sn += D.Snew_fx[(size_t)r * n + i]; D.Snew_fx[(size_t)r * n + i] = 0; }
   if (mode == 1) { D.Snew_fx[i] = sn; return; }
-  long long o = D.O_fx[i] + sn;
+  long long o = (mode == 3 ? 0 : D.O_fx[i]) + sn;
   if (j >= 0) o -= D.Sold_fx[(size_t)j * n + i];
   D.O_fx[i] = o;
   D.Snew_fx[i] = 0;

@@ -1889,7 +1889,7 @@ __global__ __launch_bounds__(256 * WPS) void k_tile(Dev D, int j) {
     if (ts >= te) return;
     if (curq >= 0) flush_run();
     od = wsumd(od); oe = wsumd(oe);
-    if (lane == 0) {
+    if (lane == 0 && !(MODE == 1 && D.head_noobj)) {      // (head_noobj: cluster_cpp's head, whose sums the first round's close overwrites unread)
       const int slotrow = (MODE == 0) ? (j % D.objslots) : 0;
       double* slot = D.objpart + ((size_t)slotrow * D.nwmax + wave) * 2;
       if (MODE == 0 && D.nb <= D.objslots) { slot[0] = od; slot[1] = oe; }  // written once per round: plain store

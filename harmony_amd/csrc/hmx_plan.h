@@ -27,6 +27,7 @@ struct Switches {
   bool sold_carry_set = false, sold_carry = false;       // HMX_SOLD_CARRY=0|1
   int shuffle_inv = 1;                                   // HMX_SHUFFLE_INV: 0 counting sort always; 2 sort-free form on sharded runs too
   bool solve_host = false;                               // HMX_MOE_SOLVE=host
+  bool solve_lds_off = false;                            // HMX_SOLVE_LDS=0: the device solve's systems in the global scratch
   bool fused_fold_off = false;                           // HMX_FUSED_FOLD=0
   int fold_impl = 0;                                     // HMX_FOLD_IMPL=split|merged -> 1 | 2: force the two-kernel fold + penalty / k_foldpen of the step loop (tests)
   int chain = -1, chain_pair = -1;                       // HMX_CHAIN / HMX_CHAIN_PAIR: 0 off | 1 forced | -1 (unset, anything else) by the thresholds
@@ -55,6 +56,7 @@ inline Switches read_switches() {
   if ((e = getenv("HMX_SHUFFLE_INV"))) s.shuffle_inv = atoi(e);
   s.solve_host = is(getenv("HMX_MOE_SOLVE"), "host");
   s.fused_fold_off = is(getenv("HMX_FUSED_FOLD"), "0");
+  s.solve_lds_off = is(getenv("HMX_SOLVE_LDS"), "0");
   e = getenv("HMX_FOLD_IMPL"); s.fold_impl = is(e, "split") ? 1 : is(e, "merged") ? 2 : 0;
   s.chain = tri(getenv("HMX_CHAIN"));
   s.chain_pair = tri(getenv("HMX_CHAIN_PAIR"));
@@ -326,6 +328,7 @@ struct RidgeGeom {
   int K = 0, KP = 0, d = 0, B = 0, C = 0, Q = 0, NCT = 0;
   int moe_mfma = 0, st_dma = 0, st_halves = 1, st_KH = 0, st_nwg = 0, wNQ = 0, wNS = 0;
   int nitems = 0, naitems = 0, grid = 2048;      // static work lists of <= 256 / <= 1024 cells; workgroups of the streaming kernels (Launch::grid)
+  int solve_lds = 0;      // Dev::solve_lds: the solve may keep its systems in LDS
 };
 enum class RidgeKind { Stats = 0, Solve = 1, Apply = 2 };
 constexpr const char* RIDGE_KIND_NAME[3] = {"stats", "solve", "apply"};
@@ -335,7 +338,10 @@ constexpr const char* RIDGE_KIND_NAME[3] = {"stats", "solve", "apply"};
 struct RidgeLaunch {
   bool valid = false, mfma = false; int p0 = 0, p1 = 0, gx = 1, gy = 1, gz = 1, threads = 0; size_t lds = 0;
   size_t lds_b_bytes = 0, lds_body_bytes = 0, lds_mask_off = 0; int rgx = 0, rgy = 0;
+  // the solve: lds_sys_off > 0 -- cov and rhs live in LDS at that byte offset, behind the `lds` bytes of the form above (which keep their meaning); lds_total = what the launch asks for
+  size_t lds_sys_off = 0, lds_total = 0;
 };
+inline size_t solve_sys_bytes(int B, int d) { return ((size_t)B + 1) * ((size_t)B + 1 + d) * sizeof(double); }      // cov [M][M] and rhs [d][M], M = B + 1
 inline RidgeLaunch plan_ridge_launch(const RidgeGeom& g, RidgeKind kind) {
   RidgeLaunch t; t.mfma = g.moe_mfma != 0;
   if (g.K < 1 || g.d < 1) return t;
@@ -350,6 +356,12 @@ inline RidgeLaunch plan_ridge_launch(const RidgeGeom& g, RidgeKind kind) {
     if (g.C > 1 && moff + maskb <= SOLVE_MASK_LDS_BYTES) { t.lds_mask_off = moff; t.lds = moff + maskb; }
     t.gx = g.K; t.threads = g.B + 1 > 48 ? 1024 : 256;
     t.valid = ints + body <= SOLVE_LDS_BYTES;      // (plan_shape: solve_on_device admits no shape beyond it)
+    t.lds_total = t.lds;
+    // (measured at 11 rows only: 37.4 -> 32.8 us per launch; what a design near the limit, ~115 rows and 150 KB of LDS per workgroup, gains or loses is not measured)
+    if (g.solve_lds) {      // the systems in LDS where they fit behind all of that (11 rows at 10 levels: 5.4 KB); larger designs keep the global scratch
+      const size_t soff = (t.lds + 7) & ~(size_t)7;
+      if (soff + solve_sys_bytes(g.B, g.d) <= SOLVE_LDS_BYTES) { t.lds_sys_off = soff; t.lds_total = soff + solve_sys_bytes(g.B, g.d); }
+    }
   } else if (kind == RidgeKind::Stats && t.mfma) {
     // slot form: 16-byte operand loads + deterministic slot reduction; a wave per PC tile incl. the ones column at index d; y: the halves of the clusters (K > 128)
     t.p0 = g.st_halves == 2 ? (g.st_KH + 15) / 16 : g.NCT;

@@ -15,6 +15,10 @@ struct RoundLedger {
   OrderSet sets[4];
   OldTable old[2]; int cur = 0;      // `cur`: what this round's block steps subtract; the other table collects the next round's
   bool sets_clean = false;           // the three replica sets are all zero
+  // The head's own tables (O, its replica set Dev::Snew_fx, the objective slots).  head_set_clean: the head's replica set is all zero -- k_fold re-zeroes what
+  // it sums, and on the chain / fold-in-prologue paths nothing else writes that buffer (the rounds use the three sets).  fresh: no head has run since setup
+  // or hmx_restart -- that head clears everything, whatever the rest of the ledger says.
+  bool head_set_clean = false, fresh = true;
 
   void sorted(uint64_t round, uint64_t seed, bool nxt) { sets[round & 3] = OrderSet{(int64_t)round, seed, nxt}; }
   void lost(uint64_t round) { sets[round & 3] = OrderSet{}; }      // (a host-provided order went into the set, or the set's run is over)
@@ -28,7 +32,10 @@ struct RoundLedger {
   void round_started() { old[cur].state = 1; sets_used(); }      // the block steps subtract `cur` and sum into the replica sets
   void tail_cleared() { old[cur].state = 0; sets_clean = true; }      // the closing launch zeroed the consumed table and the replica sets
   void flip() { cur ^= 1; }
-  void restart() { r_rewritten(); for (OrderSet& s : sets) s = OrderSet{}; }
+  void head_started() { head_set_clean = false; }      // the head's tiles sum into its replica set ...
+  void head_folded() { head_set_clean = true; fresh = false; }      // ... and k_fold behind them has been queued: zero again
+  void step_loop_used() { head_set_clean = false; }      // the launch-per-step rounds ping-pong through the head's replica set
+  void restart() { r_rewritten(); for (OrderSet& s : sets) s = OrderSet{}; head_set_clean = false; fresh = true; }
   void reset() { *this = RoundLedger{}; }
 };
 
@@ -96,8 +103,15 @@ struct HeadIn {
   bool normalise = false; int NT4 = 0, NCT = 0, upd_wps = 2;
   int max_iter_kmeans = 0; bool poll = false, r_store_always = false;
   uint64_t seed = 0; int64_t round = 0;            // the round that follows the head
+  // sharded: world > 1 || comm_force; ref_arith: any of oe_arith / obj_arith (their heads and rounds keep their own sums)
+  bool sharded = false, ref_arith = false;
 };
-struct HeadPlan { bool gather = false, fused_norm = false, files = false, clear_first = false; int r_store = 1; };
+// clear_O / clear_set / clear_objpart (and clear_first, the stale old-contribution table): what the launch in front of the head's tiles zeroes -- none: no launch.
+// skip_obj: the head leaves no objective partials (Dev::head_noobj) and no reduction follows it.
+struct HeadPlan {
+  bool gather = false, fused_norm = false, files = false, clear_first = false; int r_store = 1;
+  bool clear_O = true, clear_set = true, clear_objpart = true, skip_obj = false;
+};
 // With the round-to-round carry the head runs over the padded order of the round that FOLLOWS it (init_cluster_cpp's too) and files its R sums
 // as that round's old contributions: no pass over R between the head and the first round.
 inline bool head_gathers(const HeadIn& in) { return in.carry_ok && !in.host_order; }
@@ -113,6 +127,15 @@ inline HeadPlan plan_head(const HeadIn& in, const RoundLedger& lg) {
   // the sums filed here: the head's own rows are never read (Dev::r_store) -- 4K bytes per cell less.  (init_cluster_cpp's head is followed
   // by the caller, who may read R: it stores.)
   p.r_store = (p.files && in.normalise && in.max_iter_kmeans >= 1 && !in.poll && !in.r_store_always) ? 0 : 1;
+  // The clears.  O: k_fold behind the head overwrites it (fold mode 3) -- no clear.  The head's replica set: zero since the last head's k_fold
+  // (head_set_clean).  The objective slots: every launch that sums them zeroes what it read, so they are zero between the passes.  The first head
+  // after setup / hmx_restart, a host that provides the order, polls or asked for every R row, sharded and reference-arithmetic handles keep every
+  // clear: their calls may end or interleave in ways the ledger does not follow.
+  const bool keep_all = lg.fresh || in.host_order || in.poll || in.r_store_always || in.sharded || in.ref_arith;
+  p.clear_O = keep_all; p.clear_objpart = keep_all; p.clear_set = keep_all || !lg.head_set_clean;
+  // cluster_cpp's head (normalise) with at least one round behind it and no poll: obj[0..1] is overwritten by the first round's close before anything
+  // reads it -- hmx_cluster takes no snapshot between them --, so the head's partial sums and their reduction are not needed
+  p.skip_obj = !keep_all && in.normalise && in.max_iter_kmeans >= 1;
   return p;
 }
 

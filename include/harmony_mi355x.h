@@ -225,7 +225,8 @@ const char* hmx_p2p_status(hmx_ctx* ctx);
  * built-in RCCL all-reduce with a host-provided hook (tests: thread rendezvous, gloo). */
 int hmx_set_shard(hmx_ctx* ctx, int32_t rank, int32_t world, int64_t global_offset,
                   int64_t N_global, hmx_allreduce_fn fn, void* user);
-/* run all kernels on this hipStream_t (default: the library's own stream) */
+/* run all kernels on this hipStream_t (default: the library's own stream).  The stream must stay alive until the handle is destroyed or given another
+ * stream: another handle of the process may record an event on it (the gate between two handles' persistent launches). */
 int hmx_set_stream(hmx_ctx* ctx, void* hip_stream);
 /* optional user-interrupt poll, checked once per clustering round and per correction
  * (Progress::check_abort(), src/harmony.cpp:233,355); non-zero return aborts */

@@ -30,7 +30,8 @@ extern "C" {
  *   through the ring of page-locked slots and 128 MiB through staging of the call's own; the result does not depend on it, bit for bit);
  *   environment, read by hmx_setup: HMX_GRID, HMX_NREP, HMX_UPD_WPS (2|4), HMX_USIG=0 (general-sigma kernels),
  *   HMX_UPD_THREADS, HMX_UPD_MAXBLOCKS, HMX_STATIC_MAXBLOCKS, HMX_UPD_TPW, HMX_FUSED_FOLD=0, HMX_FOLD_IMPL=split|merged,
- *   HMX_OLDSUM_IMPL=gather|stream1, HMX_MOE_IMPL=v1 (first-generation kernels),
+ *   HMX_OLDSUM_IMPL=gather|stream1, HMX_MOE_IMPL=v1 (first-generation kernels), HMX_SOLVE_LDS=0 (the device solve's systems in the
+ *   global scratch),
  *   HMX_DOT=f32 (tile kernels: fp32-MFMA distance GEMM only; default: the split-bf16 build wherever its LDS image fits -- same
  *   fp32 accuracy);
  *   host matrices (hmx_setup / hmx_get_matrix with HMX_HOST): HMX_XFER=pin (register the caller's buffer instead of moving it
@@ -43,16 +44,18 @@ extern "C" {
  *   "sold_carry", "shuffle_inv", "need_lorder" (the shuffle also writes the cell / combination lists of the gathering old-contribution pass),
  *   "objslots" (slot rows of a round's objective partials: min(n_blocks, 64)), "upd_contig" (launch-per-step path: contiguous tile ranges per
  *   wave), "moe_mfma" (MFMA ridge kernels; 0: the first-generation ones);
- *   counters since hmx_setup: "carried_rounds" (rounds whose old contributions came from the round before, no pass over R), "rounds_without_R"
+ *   counters since hmx_setup: "diag:launches" (kernel launches of the clustering / correction launchers), "diag:event_records" (events the library recorded:
+ *   one per clustering call for the objective slots, one where a chain launch follows another stream's, two per phase in profile mode 2), "diag:gate_records" (the
+ *   chain gate's share of them: it depends on which stream of the process made the last chain launch), "carried_rounds" (rounds whose old contributions came from the round before, no pass over R), "rounds_without_R"
  *   (rounds whose R rows were not stored), "chain_rounds" (rounds run by a persistent chain);
  *   the last k_tile launch of a kind as it ran (plan_tile_launch, harmony_amd/csrc/hmx_plan.h): "launch:head" "launch:lloyd" "launch:seed" "launch:update"
  *   "launch:chain" -- 9 doubles: valid, bf (1: split-bf16 build), nct, mode, wps, usig (the instantiation k_tile<nct, mode, wps, usig>), threads, blocks,
  *   lds (bytes); -1 while the handle has not made a launch of that kind since hmx_setup;
  *   the last launch of the ridge correction of a kind as it ran (plan_ridge_launch, harmony_amd/csrc/hmx_plan.h): "launch:stats" "launch:solve" "launch:apply"
- *   -- 14 doubles: valid, mfma (0: the first-generation kernels), p0, p1 (the instantiation: k_moe_stats<p0 = DP> | k_moe_stats_q<p0 = cluster tiles of a half
+ *   -- 16 doubles: valid, mfma (0: the first-generation kernels), p0, p1 (the instantiation: k_moe_stats<p0 = DP> | k_moe_stats_q<p0 = cluster tiles of a half
  *   or of the whole, p1 = fp64 shadows in LDS> for stats, k_moe_apply<p0 = KPL, p1 = DPL> | k_moe_apply_mfma<p0 = NPT> for apply, none for solve), grid x, y, z,
- *   threads, lds (bytes), the solve's lds_b_bytes, lds_body_bytes, lds_mask_off (SolveArgs), grid x, y of k_moe_stats_reduce behind the slot statistics; -1 before
- *   the first moe_correct_ridge, and for "launch:stats" on a ridge_arith handle (its statistics are the sequential passes);
+ *   threads, lds (bytes), the solve's lds_b_bytes, lds_body_bytes, lds_mask_off (SolveArgs), grid x, y of k_moe_stats_reduce behind the slot statistics, lds_sys_off (> 0: the
+ *   solve's systems live in LDS at this offset behind the `lds` bytes; 0: global scratch), lds_total (what the solve's launch asked for; 0 for the other kinds); -1 before the first moe_correct_ridge, and for "launch:stats" on a ridge_arith handle (its statistics are the sequential passes);
  *   the plan of the last clustering round (plan_round, harmony_amd/csrc/hmx_round.h): "round:last" -- 8 doubles: path (0 persistent chain, 1 fold in the
  *   update launch's prologue, 2 step loop), merged (step loop: k_foldpen instead of k_fold + k_penalty), chain_tail (the chain closed the round itself),
  *   carried (old contributions filed by the pass before: no pass over R), write_next (it filed the next round's), r_store (0: its R rows were not

@@ -96,6 +96,16 @@ try:
 except Exception as e:       # noqa: BLE001
     missing.append("scaling_prediction.py: %s" % e)
 
+ab = js("launch_path_ab.json")      # parent and change alternating, five plain bench lines each
+if ab:
+    side = {k: [r["ms_per_step"] for r in ab["runs"] if r["side"] == k] for k in ("parent", "change")}
+    mean = {k: sum(v) / len(v) for k, v in side.items()}
+    sd = {k: (sum((x - mean[k]) ** 2 for x in v) / (len(v) - 1)) ** 0.5 for k, v in side.items()}
+    diff, bar = mean["parent"] - mean["change"], 3 * max(sd.values())
+    vals["LP_AB"] = ("parent %s ms per step (mean of %d, standard deviation %s), change %s (%s): %s ms or %s %% less; three times the larger standard deviation is %s ms -- %s."
+                     % (fmt(mean["parent"], 3), len(side["parent"]), fmt(sd["parent"], 3), fmt(mean["change"], 3), fmt(sd["change"], 3), fmt(diff, 3), fmt(100 * diff / mean["parent"], 1),
+                        fmt(bar, 3), "the gain counts" if diff > bar else "the difference does NOT clear that bar"))
+
 lb = line("r7_lisi_bench.json")      # tools/lisi_bench.py
 if lb:
     kt = "; ".join("%s %.1f ms" % (k["kernel"].split("(")[0].replace("void hmx::", ""), k["total_ms"]) for k in lb.get("kernel_trace", []))

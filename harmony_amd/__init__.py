@@ -7,6 +7,7 @@ object) over the C ABI in include/harmony_mi355x.h.  All numerics run in hand-wr
 from .graph import connected_components, graph_connectivity, graph_from_knn, neighbors
 from .group_stats import gene_stats_by_group, markers_from_sums, rank_genes_groups, variable_genes
 from .harmony_obj import Harmony, HarmonyError
+from .leiden import leiden
 from .louvain import louvain
 from .mapping import HarmonyReference, map_query, mapping_confidence
 from .metrics import compute_lisi, knn, knn_predict, lisi_from_knn
@@ -25,4 +26,4 @@ __all__ = ["RunHarmony", "harmony_options", "Harmony", "HarmonyError", "harmoniz
            "silhouette_samples", "silhouette_label", "silhouette_batch", "HarmonyLoadings", "project_query", "map_query_counts", "gene_stats", "fit_loadings",
            "gene_stats_by_group", "variable_genes", "rank_genes_groups", "markers_from_sums",
            "rank_sums_by_group", "wilcoxon_from_rank_sums", "neighbors", "graph_from_knn", "connected_components", "graph_connectivity",
-           "snn", "snn_from_knn", "louvain", "umap", "umap_layout", "find_ab_params"]
+           "snn", "snn_from_knn", "louvain", "leiden", "umap", "umap_layout", "find_ab_params"]

@@ -133,6 +133,11 @@ LOUVAIN_SIGNATURES = {
     "hmx_louvain": (C.c_int, [C.c_void_p, _lp, _ip, _fp, C.c_int64, C.c_double, C.c_int32, C.c_int32, _ip, _ip, _dp, _ip, _ip, _dp]),
 }
 
+# the symbol include/harmony_mi355x_leiden.h declares (Leiden clustering of a neighbour graph)
+LEIDEN_SIGNATURES = {
+    "hmx_leiden": (C.c_int, [C.c_void_p, _lp, _ip, _fp, C.c_int64, C.c_double, C.c_int32, C.c_int32, _ip, _ip, _dp, _ip, _ip, _ip, _ip, _ip, _dp]),
+}
+
 # the symbol include/harmony_mi355x_umap.h declares (the UMAP layout of a neighbour graph)
 UMAP_SIGNATURES = {
     "hmx_umap_layout": (C.c_int, [C.c_void_p, _lp, _ip, _fp, C.c_int64, C.c_int32, _fp, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double,
@@ -159,7 +164,8 @@ def load():
     for name, (res, args) in (list(SIGNATURES.items()) + list(METRICS_SIGNATURES.items()) + list(SILHOUETTE_SIGNATURES.items())
                               + list(CONFIDENCE_SIGNATURES.items()) + list(PROJECT_SIGNATURES.items()) + list(PCA_SIGNATURES.items())
                               + list(GROUPS_SIGNATURES.items()) + list(RANKSUM_SIGNATURES.items()) + list(GRAPH_SIGNATURES.items())
-                              + list(SNN_SIGNATURES.items()) + list(LOUVAIN_SIGNATURES.items()) + list(UMAP_SIGNATURES.items())):
+                              + list(SNN_SIGNATURES.items()) + list(LOUVAIN_SIGNATURES.items()) + list(UMAP_SIGNATURES.items())
+                              + list(LEIDEN_SIGNATURES.items())):
         fn = getattr(lib, name)  # AttributeError if the ABI and the header drift apart
         fn.restype = res
         fn.argtypes = args

@@ -13,6 +13,7 @@
 #include "../../include/harmony_mi355x_graph.h"  // (the neighbour graph and its components: hmx_api_graph.inc)
 #include "../../include/harmony_mi355x_snn.h"  // (Seurat's shared-nearest-neighbour graph: hmx_api_snn.inc)
 #include "../../include/harmony_mi355x_louvain.h"  // (Louvain clustering of such a graph: hmx_api_louvain.inc)
+#include "../../include/harmony_mi355x_leiden.h"  // (Leiden clustering of such a graph: hmx_api_leiden.inc)
 #include "../../include/harmony_mi355x_umap.h"  // (the UMAP layout of such a graph: hmx_api_umap.inc)
 #include "hmx_internal.h"
 #include "hmx_rrng.h"
@@ -22,6 +23,7 @@
 #include "hmx_ranksum_plan.h"
 #include "hmx_graph.h"
 #include "hmx_louvain.h"
+#include "hmx_leiden.h"
 #include "hmx_umap.h"
 #include "hmx_xfer_pool.h"
 
@@ -381,4 +383,5 @@ int hmx_moe_correct_ridge(hmx_ctx* ctx) {  // src/harmony.cpp:345-638
 #include "hmx_api_graph.inc"
 #include "hmx_api_snn.inc"
 #include "hmx_api_louvain.inc"
+#include "hmx_api_leiden.inc"
 #include "hmx_api_umap.inc"

@@ -183,6 +183,12 @@ int64_t hmx_get(hmx_ctx* ctx, const char* field, double* out, int64_t cap) {
   if (f == "louvain:sweeps") return scalar((double)ctx->louvain_sweeps);
   if (f == "louvain:clusters") return scalar((double)ctx->louvain_clusters);
   if (f == "louvain:long_rows") return scalar((double)ctx->louvain_long_rows);      // ... and the rows of level 0 above the short path's cap
+  if (f == "leiden:levels") return scalar((double)ctx->leiden_levels);      // the last hmx_leiden: recorded levels, sweeps of local moves and of refinement over all levels, clusters
+  if (f == "leiden:sweeps") return scalar((double)ctx->leiden_sweeps);
+  if (f == "leiden:refine_sweeps") return scalar((double)ctx->leiden_refine_sweeps);
+  if (f == "leiden:clusters") return scalar((double)ctx->leiden_clusters);
+  if (f == "leiden:converged") return scalar((double)ctx->leiden_converged);
+  if (f == "leiden:long_rows") return scalar((double)ctx->leiden_long_rows);      // ... and the rows of level 0 (edges only) above the short path's cap
   if (f == "louvain:short_cap") return scalar((double)(ctx->louvain_short_cap >= 0 ? std::min<int64_t>(ctx->louvain_short_cap, LV_SHORT_CAP) : LV_SHORT_CAP));
   if (f == "umap:fired") return scalar((double)ctx->umap_fired);      // the last hmx_umap_layout: directed firings of its epochs, the epochs run, the rows above the short path's cap
   if (f == "umap:epochs") return scalar((double)ctx->umap_epochs);

@@ -195,6 +195,8 @@ struct hmx_ctx {
   // ---- Louvain clustering (hmx_louvain): the counters of the last call ("louvain:levels" ...) and the lab field "louvain_short_cap", a cap
   // below the short path's own on the entries of a row it takes (-1: the default)
   int64_t louvain_levels = 0, louvain_best_level = 0, louvain_sweeps = 0, louvain_clusters = 0, louvain_long_rows = 0, louvain_short_cap = -1;
+  // ---- Leiden clustering (hmx_leiden): the counters of the last call ("leiden:levels" ...); the short path's cap is Louvain's lab field
+  int64_t leiden_levels = 0, leiden_sweeps = 0, leiden_refine_sweeps = 0, leiden_clusters = 0, leiden_converged = 0, leiden_long_rows = 0;
   // ---- the UMAP layout (hmx_umap_layout): the counters of the last call ("umap:fired" ...) and the lab field "umap_short_cap", the entries of
   // a row the one-wave path takes in place of its own cap (-1: the default)
   int64_t umap_fired = 0, umap_epochs = 0, umap_long_rows = 0, umap_short_cap = -1;

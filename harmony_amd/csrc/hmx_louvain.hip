@@ -15,31 +15,10 @@
 //                         heads counted / coarse indices and sums written behind the scanned lengths, the cells' labels composed.
 // Every loop has a bound known on entry; no kernel waits for another workgroup; integer atomics only.
 #include "hmx_louvain.h"
+#include "hmx_lv_device.h"
 
 namespace hmx {
-typedef unsigned long long u64;
 
-__device__ __forceinline__ unsigned lv_fmix32(unsigned x) {
-  x ^= x >> 16; x *= 0x85ebca6bu; x ^= x >> 13; x *= 0xc2b2ae35u; x ^= x >> 16;
-  return x;
-}
-__device__ __forceinline__ int lv_bucket(long long i, unsigned key) { return (int)(lv_fmix32((unsigned)i ^ key) & (LV_SUBROUNDS - 1)); }
-// dbl(w) - kg * dbl(t): three correctly rounded operations, never fused.  (__dmul_rn is a plain product to the compiler, which contracts it
-// with the difference into one fma under the default -ffp-contract=fast; the empty asm makes the rounded product a value of its own.)
-__device__ __forceinline__ double lv_score(long long w, double kg, long long t) {
-#pragma clang fp contract(off)
-  double p = __dmul_rn(kg, __ll2double_rn(t));
-  asm volatile("" : "+v"(p));
-  return __dsub_rn(__ll2double_rn(w), p);
-}
-__device__ __forceinline__ double lv_kg(long long k, double g) {
-#pragma clang fp contract(off)
-  return __dmul_rn(__ll2double_rn(k), g);
-}
-// a candidate (s, c) against the best so far: the larger score, ties to the smaller community
-__device__ __forceinline__ void lv_better(bool& has, double& bs, int& bc, bool h, double s, int c) {
-  if (h && (!has || s > bs || (s == bs && c < bc))) { has = true; bs = s; bc = c; }
-}
 __device__ __forceinline__ int lv_lower_bound(const int* v, int n, int key) {
   int lo = 0, hi = n;
   while (lo < hi) {

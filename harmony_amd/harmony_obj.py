@@ -330,12 +330,25 @@ class Harmony(object):
         from .snn import harmony_snn
         return harmony_snn(self, k, prune)
 
-    def clusters(self, k=20, prune=1.0 / 15.0, resolution=0.8):
+    def clusters(self, k=20, prune=1.0 / 15.0, resolution=0.8, algorithm="louvain"):
         """Seurat's FindNeighbors and FindClusters on the handle's current Z_corr: the SNN graph (snn) and its Louvain clusters
         (louvain.louvain) at `resolution`; the defaults are Seurat's.  Returns (labels, n_clusters, modularity, levels), labels in the order
-        the cells were given in, 0 the largest cluster."""
+        the cells were given in, 0 the largest cluster.  algorithm="leiden" (Seurat's algorithm = 4) clusters the same graph with
+        leiden.leiden and returns its (labels, n_clusters, modularity, levels, converged)."""
+        if algorithm == "leiden":
+            from .leiden import harmony_clusters_leiden
+            return harmony_clusters_leiden(self, k, prune, resolution)
+        if algorithm != "louvain":
+            raise ValueError('algorithm must be "louvain" or "leiden"')
         from .louvain import harmony_clusters
         return harmony_clusters(self, k, prune, resolution)
+
+    def leiden(self, n_neighbors=15, resolution=1.0):
+        """scanpy's neighbors and leiden on the handle's current Z_corr: the connectivities of the neighbour graph (neighbors) and their
+        Leiden clusters (leiden.leiden) at `resolution`; the defaults are scanpy's.  Returns (labels, n_clusters, modularity, levels,
+        converged), labels in the order the cells were given in, 0 the largest cluster."""
+        from .leiden import harmony_leiden
+        return harmony_leiden(self, n_neighbors, resolution)
 
     def umap(self, n_neighbors=15, min_dist=0.5, **kwargs):
         """The UMAP layout (umap.umap) of the handle's current Z_corr: its neighbour graph (neighbors) laid out from the top principal axes;

@@ -322,6 +322,26 @@ if um:
         missing.append("umap_kernel_stats.csv")
 else:
     vals["UMAP_MEASURED"] = "**Not measured yet**: `profiles/umap_bench.json` (written by `tools/umap_bench.py` on an MI355X) is not in the tree."
+ldn = line("leiden_bench.json")      # tools/leiden_bench.py
+if ldn:
+    def ld_text(u):
+        return ("the SNN graph of %s cells x %d PCs at k = %d, %s entries, resolution %.1f, median of %d calls: `\"timer:leiden\"` **%.0f ms** (spread %.1f %%) -- local "
+                "moves and the levels' records %.0f ms, refinement with its `cut` %.0f ms, aggregation %.0f ms -- for %d levels, %d sweeps of moves and %d of "
+                "refinement: %s clusters over %s nodes per level, %d clusters at Q %.5f, converged: %s, %d components inside them; `\"timer:louvain\"` on the same "
+                "handle and graph %.0f ms (spread %.1f %%), %d clusters at Q %.5f with %d components inside them; %d rows on the long path; the same bits in every call: %s"
+                % ("{:,}".format(u["cells"]).replace(",", " "), u["d"], u["k"], "{:,}".format(u["entries"]).replace(",", " "), u["resolution"], len(u["leiden_ms_all"]),
+                   u["leiden_ms"], 100.0 * u["leiden_spread"], u["leiden_moves_ms"], u["leiden_refine_ms"], u["leiden_aggregate_ms"], u["levels"], u["sweeps"],
+                   u["refine_sweeps"], " → ".join(str(c) for c in u["level_clusters"]), " → ".join(str(c) for c in u["level_nodes"]), u["clusters"], u["modularity"],
+                   "yes" if u["converged"] else "NO", u["components_within_clusters"], u["louvain_ms"], 100.0 * u["louvain_spread"], u["louvain_clusters"],
+                   u["louvain_modularity"], u["louvain_components_within_clusters"], u["long_rows"], "yes" if u["same_bits_every_call"] else "NO"))
+    vals["LEIDEN_MEASURED"] = ("**Measured** (`profiles/leiden_bench.json`, one MI355X, `tools/leiden_bench.py`; both timers include the upload of the CSR; `cut` is the "
+                               "recomputed form and interleaves with the refinement's decisions on the stream, so the two are one figure): " + ld_text(ldn) + ".")
+    sm = line("leiden_bench_100k.json")
+    if sm:
+        vals["LEIDEN_MEASURED"] += " At " + ld_text(sm) + " (`profiles/leiden_bench_100k.json`)."
+else:
+    vals["LEIDEN_MEASURED"] = ("**Nothing has been measured on a device yet**: `profiles/leiden_bench.json` (written by `tools/leiden_bench.py` on an MI355X, which times "
+                               "`hmx_leiden` beside `hmx_louvain` on the same SNN graphs at 100k and 1M cells, with the phases' times) is not in the tree.")
 parts = sorted(f for f in os.listdir(os.path.join(ROOT, "docs", "design_parts")) if f.endswith(".md"))
 out = io.StringIO()
 for f in parts:

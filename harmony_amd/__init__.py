@@ -19,6 +19,7 @@ from .silhouette import silhouette_batch, silhouette_label, silhouette_samples
 from .snn import snn, snn_from_knn
 from .ui import RunHarmony, prepare_setup_args
 from .umap import find_ab_params, umap, umap_layout
+from .umap_transform import umap_query_weights, umap_transform, umap_transform_from_knn
 from .utils import harmonize
 
 __all__ = ["RunHarmony", "harmony_options", "Harmony", "HarmonyError", "harmonize", "prepare_setup_args", "map_query",
@@ -26,4 +27,5 @@ __all__ = ["RunHarmony", "harmony_options", "Harmony", "HarmonyError", "harmoniz
            "silhouette_samples", "silhouette_label", "silhouette_batch", "HarmonyLoadings", "project_query", "map_query_counts", "gene_stats", "fit_loadings",
            "gene_stats_by_group", "variable_genes", "rank_genes_groups", "markers_from_sums",
            "rank_sums_by_group", "wilcoxon_from_rank_sums", "neighbors", "graph_from_knn", "connected_components", "graph_connectivity",
-           "snn", "snn_from_knn", "louvain", "leiden", "umap", "umap_layout", "find_ab_params"]
+           "snn", "snn_from_knn", "louvain", "leiden", "umap", "umap_layout", "find_ab_params",
+           "umap_query_weights", "umap_transform_from_knn", "umap_transform"]

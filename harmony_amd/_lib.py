@@ -144,6 +144,13 @@ UMAP_SIGNATURES = {
                                   C.c_double, C.c_double, C.c_int32, C.c_uint32, _fp]),
 }
 
+# the symbols include/harmony_mi355x_umap_transform.h declares (query cells put into a fitted UMAP layout)
+UMAP_TRANSFORM_SIGNATURES = {
+    "hmx_umap_query_weights": (C.c_int, [C.c_void_p, _ip, _fp, C.c_int64, C.c_int32, C.c_int64, _fp, _dp]),
+    "hmx_umap_transform": (C.c_int, [C.c_void_p, _ip, _fp, C.c_int64, C.c_int32, _fp, C.c_int64, C.c_int32, _fp, C.c_int32, C.c_int32, C.c_int32,
+                                     C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_uint32, _fp, _fp]),
+}
+
 _lib = None
 
 
@@ -165,7 +172,7 @@ def load():
                               + list(CONFIDENCE_SIGNATURES.items()) + list(PROJECT_SIGNATURES.items()) + list(PCA_SIGNATURES.items())
                               + list(GROUPS_SIGNATURES.items()) + list(RANKSUM_SIGNATURES.items()) + list(GRAPH_SIGNATURES.items())
                               + list(SNN_SIGNATURES.items()) + list(LOUVAIN_SIGNATURES.items()) + list(UMAP_SIGNATURES.items())
-                              + list(LEIDEN_SIGNATURES.items())):
+                              + list(LEIDEN_SIGNATURES.items()) + list(UMAP_TRANSFORM_SIGNATURES.items())):
         fn = getattr(lib, name)  # AttributeError if the ABI and the header drift apart
         fn.restype = res
         fn.argtypes = args

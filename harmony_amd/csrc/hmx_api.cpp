@@ -15,6 +15,7 @@
 #include "../../include/harmony_mi355x_louvain.h"  // (Louvain clustering of such a graph: hmx_api_louvain.inc)
 #include "../../include/harmony_mi355x_leiden.h"  // (Leiden clustering of such a graph: hmx_api_leiden.inc)
 #include "../../include/harmony_mi355x_umap.h"  // (the UMAP layout of such a graph: hmx_api_umap.inc)
+#include "../../include/harmony_mi355x_umap_transform.h"  // (query cells in a fitted layout: hmx_api_umap_transform.inc)
 #include "hmx_internal.h"
 #include "hmx_rrng.h"
 #include "hmx_plan.h"
@@ -25,6 +26,7 @@
 #include "hmx_louvain.h"
 #include "hmx_leiden.h"
 #include "hmx_umap.h"
+#include "hmx_umap_transform.h"
 #include "hmx_xfer_pool.h"
 
 #include <dlfcn.h>
@@ -385,3 +387,4 @@ int hmx_moe_correct_ridge(hmx_ctx* ctx) {  // src/harmony.cpp:345-638
 #include "hmx_api_louvain.inc"
 #include "hmx_api_leiden.inc"
 #include "hmx_api_umap.inc"
+#include "hmx_api_umap_transform.inc"

@@ -194,6 +194,8 @@ int64_t hmx_get(hmx_ctx* ctx, const char* field, double* out, int64_t cap) {
   if (f == "umap:epochs") return scalar((double)ctx->umap_epochs);
   if (f == "umap:long_rows") return scalar((double)ctx->umap_long_rows);
   if (f == "umap:short_cap") return scalar((double)(ctx->umap_short_cap >= 0 ? ctx->umap_short_cap : UM_SHORT_CAP));
+  if (f == "umap_transform:fired") return scalar((double)ctx->umap_transform_fired);      // the last hmx_umap_transform: firings of its epochs over all cells, the epochs run
+  if (f == "umap_transform:epochs") return scalar((double)ctx->umap_transform_epochs);
   if (f == "diag:launches") return scalar((double)ctx->n_launches);      // since setup: kernel launches of the clustering / correction launchers (hmx_k_launch.inc; copies and memsets are not kernels of ours)
   if (f == "diag:event_records") return scalar((double)ctx->n_event_records);      // ... and events recorded (objective slots, the chain gate across streams, profile mode's phases)
   if (f == "diag:gate_records") return scalar((double)ctx->n_gate_records);      // ... those of them that were the chain gate's: they depend on which stream of the PROCESS launched a chain last

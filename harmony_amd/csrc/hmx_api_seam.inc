@@ -200,6 +200,8 @@ struct hmx_ctx {
   // ---- the UMAP layout (hmx_umap_layout): the counters of the last call ("umap:fired" ...) and the lab field "umap_short_cap", the entries of
   // a row the one-wave path takes in place of its own cap (-1: the default)
   int64_t umap_fired = 0, umap_epochs = 0, umap_long_rows = 0, umap_short_cap = -1;
+  // ---- query cells in a fitted layout (hmx_umap_transform): the counters of the last call ("umap_transform:fired", "umap_transform:epochs")
+  int64_t umap_transform_fired = 0, umap_transform_epochs = 0;
   // ---- the reference's PCA (hmx_pca_prepare / apply / release, hmx_api_pca.inc): the prepared lists (a PcaState) and their entry count
   std::shared_ptr<void> pca; int64_t pca_entries = 0;
   QueryDev qd{};            // the query's device tables (rows in D.Zo / D.Zc, internal order in D.perm / D.invperm)

@@ -13,33 +13,10 @@
 //   k_um_fired            the rows' firing counters added up (integers).
 // Every loop has a bound known on entry; no kernel waits for another workgroup; integer atomics only; no LDS but the long path's partials.
 #include "hmx_umap.h"
+#include "hmx_um_device.h"      // um_fmix32, um_load, um_clip, um_term: shared with hmx_umap_transform.hip
 
 namespace hmx {
 
-__device__ __forceinline__ unsigned um_fmix32(unsigned x) {
-  x ^= x >> 16; x *= 0x85ebca6bu; x ^= x >> 13; x *= 0xc2b2ae35u; x ^= x >> 16;
-  return x;
-}
-template <int DIM>
-__device__ __forceinline__ void um_load(const float* Y, long long i, float& x, float& y, float& z) {
-  if (DIM == 2) { const float2 p = *reinterpret_cast<const float2*>(Y + 2 * i); x = p.x; y = p.y; z = 0.0f; }
-  else { x = Y[3 * i]; y = Y[3 * i + 1]; z = Y[3 * i + 2]; }
-}
-__device__ __forceinline__ float um_clip(float v) { return fminf(fmaxf(v, -4.0f), 4.0f); }
-// one term of the sum from the difference y_i - y_other: the attraction 2 clip(c_a d) or the repulsion clip(c_r d); d2^b = exp2(b log2 d2)
-template <int DIM, bool ATTRACT>
-__device__ __forceinline__ void um_term(const UmDev& D, float dx, float dy, float dz, float& ax, float& ay, float& az) {
-  float d2 = dx * dx + dy * dy;
-  if (DIM == 3) d2 += dz * dz;
-  if (!(d2 > 0.0f)) return;
-  const float pw = exp2f(D.b * log2f(d2));
-  const float den = D.a * pw + 1.0f;
-  const float c = ATTRACT ? (D.m2ab * pw) / (d2 * den) : D.g2b / ((0.001f + d2) * den);
-  const float f = ATTRACT ? 2.0f : 1.0f;
-  ax += f * um_clip(c * dx);
-  ay += f * um_clip(c * dy);
-  if (DIM == 3) az += f * um_clip(c * dz);
-}
 // entry e of row i: 1 if it fired.  r = dbl(w) / dbl(wmax); fires iff floor(dbl(n + 1) r) > floor(dbl(n) r)
 template <int DIM>
 __device__ __forceinline__ unsigned um_entry(const UmDev& D, long long i, long long e, float xi, float yi, float zi, float& ax, float& ay, float& az) {

@@ -357,6 +357,15 @@ class Harmony(object):
         from .umap import harmony_umap
         return harmony_umap(self, n_neighbors, min_dist, **kwargs)
 
+    def umap_transform(self, reference, reference_layout, **kwargs):
+        """The handle's current Z_corr put into a fitted UMAP layout (umap_transform.umap_transform): `reference` the reference's cells x PCs
+        in the same corrected space, `reference_layout` its fitted positions [Nr, 2 or 3], which stay as they are; further arguments
+        (n_neighbors, init, n_epochs, min_dist, spread, a, b, gamma, learning_rate, negative_sample_rate, seed, return_init, device) as
+        umap_transform takes them.  Works on a fitted handle and on the object map_query(return_object=True) returns.  Returns float32
+        positions [N, n_components] in the order the cells were given in; two calls give identical coordinates."""
+        from .umap_transform import harmony_umap_transform
+        return harmony_umap_transform(self, reference, reference_layout, **kwargs)
+
     def silhouette(self, meta_data, label_col, group_col=None, return_ab=False):
         """Silhouette widths (silhouette.silhouette_samples) of the handle's current Z_corr over the column `label_col` of meta_data, within the
         levels of `group_col` when one is named; one label per cell in the order the cells were given in.  Returns s, or (s, a, b).  Z_corr

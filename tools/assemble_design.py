@@ -342,6 +342,37 @@ if ldn:
 else:
     vals["LEIDEN_MEASURED"] = ("**Nothing has been measured on a device yet**: `profiles/leiden_bench.json` (written by `tools/leiden_bench.py` on an MI355X, which times "
                                "`hmx_leiden` beside `hmx_louvain` on the same SNN graphs at 100k and 1M cells, with the phases' times) is not in the tree.")
+ut = line("umap_transform_bench.json")      # tools/umap_transform_bench.py
+if ut:
+    def ut_text(r):
+        return ("%s query cells, %d epochs: the search `\"timer:knn\"` %.0f ms; `\"timer:umap_query_weights\"` **%.2f ms** (spread %.0f %%); `\"timer:umap_transform\"` "
+                "**%.2f ms** (spread %.0f %%), of which %.2f ms are the uploads (%.0f MB) and the start (a call that asks for no epoch) and **%.3f ms** the epochs' one "
+                "kernel (`\"timer:umap_transform_epochs\"`, between two events; spread %.1f %%): %s firings, %.1f per cell and epoch, **%.3f ns per firing**, "
+                "%.0f MB of sampled positions gathered (%.2f TB/s of useful bytes); with the lists and samples folded onto 1024 reference cells the kernel takes "
+                "%.3f ms, so %.0f %% of its time goes with the gathers' misses; the same bits in every call: %s; mean |Y - Y0| %.3f"
+                % ("{:,}".format(r["query"]).replace(",", " "), r["epochs"], r["knn_ms"], r["weights_ms"], 100.0 * r["weights_spread"], r["transform_ms"],
+                   100.0 * r["transform_spread"], r["front_ms"], r["upload_bytes"] / 1e6, r["epochs_ms"], 100.0 * r["epochs_spread"],
+                   "{:,}".format(r["fired"]).replace(",", " "), r["firings_per_cell_epoch"], r["ns_per_firing"], r["gather_bytes"] / 1e6, r["gather_TBps"],
+                   r["cached_epochs_ms"], 100.0 * r["gather_share"], "yes" if r["same_bits_every_call"] else "NO", r["mean_move"]))
+    big = ut["runs"][0]
+    vals["UMAP_TRANSFORM_MEASURED"] = (
+        "**Measured** (`profiles/umap_transform_bench.json`, one MI355X, `tools/umap_transform_bench.py`: a reference of %s cells x %d PCs laid out by `umap()`, "
+        "k = %d, medians of %d calls after %d; the wall timers are a few milliseconds of copies from pageable memory and spread accordingly, the kernel's "
+        "time does not): " % ("{:,}".format(ut["reference"]).replace(",", " "), ut["d"], ut["k"], ut["repeats"], ut["warmup"])
+        + "; ".join(ut_text(r) for r in ut["runs"]) + ". "
+        + ("`hmx_umap_layout` spends %.3f ns per firing at 10\u2076 cells (`profiles/umap_bench.json`: an epoch's time over its firings), %.1f times as much: there a "
+           "firing also gathers its attraction's other end, walks the CSR and writes a snapshot per epoch. " % (ut["layout_ns_per_firing"], ut["layout_ns_per_firing"] / big["ns_per_firing"])
+           if ut.get("layout_ns_per_firing") else "")
+        + "**What bounds the kernel: the sample gathers, not the dependent chain.** At %s query cells %s firings x %d samples are %.0f million 8-byte reads, each its "
+          "own 64-byte line of an 8 MB array: %.1f TB/s of lines, against about 8.6 TB/s measured for random rows out of the Infinity Cache (\u00a76m). The per-epoch "
+          "chain (`log2f`/`exp2f`, the butterfly, the fp64 firing test) is what is left when every gather hits: %.0f %% of the time. With few cells (10\u2074: 2 500 "
+          "waves on 1 024 SIMDs) the chain's share grows, since there are too few waves to hide either latency."
+          % ("{:,}".format(big["query"]).replace(",", " "), "{:,}".format(big["fired"]).replace(",", " "), big["negative_sample_rate"],
+             big["fired"] * big["negative_sample_rate"] / 1e6, big["fired"] * big["negative_sample_rate"] * 64.0 / big["epochs_ms"] / 1e9,
+             100.0 * (1.0 - big["gather_share"])))
+else:
+    vals["UMAP_TRANSFORM_MEASURED"] = ("**Not measured yet**: `profiles/umap_transform_bench.json` (written by `tools/umap_transform_bench.py` on an MI355X) is not "
+                                       "in the tree.")
 parts = sorted(f for f in os.listdir(os.path.join(ROOT, "docs", "design_parts")) if f.endswith(".md"))
 out = io.StringIO()
 for f in parts:

@@ -4,6 +4,7 @@ Host-side mirror of the reference's R API (RunHarmony / harmony_options / the `h
 object) over the C ABI in include/harmony_mi355x.h.  All numerics run in hand-written HIP
 (harmony_amd/csrc); there is no CPU fallback.
 """
+from .doublets import doublet_neighbors, doublet_scores_from_counts, doublet_threshold, scrub_doublets, simulate_doublets
 from .graph import connected_components, graph_connectivity, graph_from_knn, neighbors
 from .group_stats import gene_stats_by_group, markers_from_sums, rank_genes_groups, variable_genes
 from .harmony_obj import Harmony, HarmonyError
@@ -28,4 +29,5 @@ __all__ = ["RunHarmony", "harmony_options", "Harmony", "HarmonyError", "harmoniz
            "gene_stats_by_group", "variable_genes", "rank_genes_groups", "markers_from_sums",
            "rank_sums_by_group", "wilcoxon_from_rank_sums", "neighbors", "graph_from_knn", "connected_components", "graph_connectivity",
            "snn", "snn_from_knn", "louvain", "leiden", "umap", "umap_layout", "find_ab_params",
-           "umap_query_weights", "umap_transform_from_knn", "umap_transform"]
+           "umap_query_weights", "umap_transform_from_knn", "umap_transform",
+           "simulate_doublets", "doublet_neighbors", "doublet_scores_from_counts", "doublet_threshold", "scrub_doublets"]

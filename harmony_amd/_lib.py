@@ -151,6 +151,13 @@ UMAP_TRANSFORM_SIGNATURES = {
                                      C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_uint32, _fp, _fp]),
 }
 
+# the symbols include/harmony_mi355x_doublets.h declares (synthetic doublets in PC space, synthetic neighbours per cell)
+DOUBLETS_SIGNATURES = {
+    "hmx_simulate_doublets": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, _ip,
+                                        _dp, _dp, _dp, C.c_int32, C.c_int32, C.c_double, C.c_double, _dp, C.c_int64, _lp, C.c_void_p, C.c_int32]),
+    "hmx_doublet_neighbors": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _ip, _ip, _fp]),
+}
+
 _lib = None
 
 
@@ -172,7 +179,7 @@ def load():
                               + list(CONFIDENCE_SIGNATURES.items()) + list(PROJECT_SIGNATURES.items()) + list(PCA_SIGNATURES.items())
                               + list(GROUPS_SIGNATURES.items()) + list(RANKSUM_SIGNATURES.items()) + list(GRAPH_SIGNATURES.items())
                               + list(SNN_SIGNATURES.items()) + list(LOUVAIN_SIGNATURES.items()) + list(UMAP_SIGNATURES.items())
-                              + list(LEIDEN_SIGNATURES.items()) + list(UMAP_TRANSFORM_SIGNATURES.items())):
+                              + list(LEIDEN_SIGNATURES.items()) + list(UMAP_TRANSFORM_SIGNATURES.items()) + list(DOUBLETS_SIGNATURES.items())):
         fn = getattr(lib, name)  # AttributeError if the ABI and the header drift apart
         fn.restype = res
         fn.argtypes = args

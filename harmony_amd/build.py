@@ -10,10 +10,10 @@ import subprocess
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = [os.path.join(HERE, "csrc", f) for f in ("hmx_kernels.hip", "hmx_tile_bf.hip", "hmx_seq.hip", "hmx_query.hip", "hmx_confidence.hip", "hmx_project.hip", "hmx_pca.hip", "hmx_ranksum.hip", "hmx_graph.hip", "hmx_louvain.hip", "hmx_leiden.hip", "hmx_umap.hip", "hmx_umap_transform.hip", "hmx_knn.hip", "hmx_silhouette.hip", "hmx_api.cpp")]
+SRC = [os.path.join(HERE, "csrc", f) for f in ("hmx_kernels.hip", "hmx_tile_bf.hip", "hmx_seq.hip", "hmx_query.hip", "hmx_confidence.hip", "hmx_project.hip", "hmx_pca.hip", "hmx_ranksum.hip", "hmx_graph.hip", "hmx_louvain.hip", "hmx_leiden.hip", "hmx_umap.hip", "hmx_umap_transform.hip", "hmx_doublets.hip", "hmx_knn.hip", "hmx_silhouette.hip", "hmx_api.cpp")]
 # (hmx_tile_bf.hip is hmx_kernels.hip's tile kernel built a second time with the split-bf16 distance GEMM: it includes that file)
 _INC = [os.path.join(HERE, "csrc", f) for f in ("hmx_k_stream.inc", "hmx_k_tile.inc", "hmx_k_correct.inc", "hmx_k_launch.inc")]      # the kernels, by section (included by hmx_kernels.hip)
-_API_INC = [os.path.join(HERE, "csrc", "hmx_api_%s.inc" % f) for f in ("xfer", "seam", "kmeans", "refarith", "update", "ridge", "p2p", "setup", "query", "diag", "call", "metrics", "silhouette", "confidence", "csr", "project", "pca", "groups", "ranksum", "graph", "snn", "louvain", "leiden", "umap", "umap_transform")]    # the host orchestration, by section (included by hmx_api.cpp)
+_API_INC = [os.path.join(HERE, "csrc", "hmx_api_%s.inc" % f) for f in ("xfer", "seam", "kmeans", "refarith", "update", "ridge", "p2p", "setup", "query", "diag", "call", "metrics", "silhouette", "confidence", "csr", "project", "pca", "groups", "ranksum", "graph", "snn", "louvain", "leiden", "umap", "umap_transform", "doublets")]    # the host orchestration, by section (included by hmx_api.cpp)
 _PLAN = [os.path.join(HERE, "csrc", "hmx_plan.h")]      # the launch plan (host code only): of a fit for hmx_setup (hmx_api.cpp), of every k_tile launch for the tile launchers
 _API_INC += _PLAN + [os.path.join(HERE, "csrc", "hmx_round.h")]      # (hmx_round.h: the round plan and ledger of update_R / head_pass, hmx_api.cpp only)
 _API_INC += [os.path.join(HERE, "csrc", "hmx_xfer_pool.h")]      # (the host threads of the host matrix seam, hmx_api_xfer.inc: host code only)
@@ -29,7 +29,9 @@ _UMAP = _LOUVAIN + [os.path.join(HERE, "csrc", "hmx_umap.h"), os.path.join(HERE,
 _API_INC += _UMAP[len(_LOUVAIN):]
 _UMAP_TRANSFORM = _UMAP + [os.path.join(HERE, "csrc", "hmx_umap_transform.h"), os.path.join(HERE, "..", "include", "harmony_mi355x_umap_transform.h")]      # query cells in a fitted layout: hmx_umap_transform.hip and hmx_api.cpp only
 _API_INC += _UMAP_TRANSFORM[len(_UMAP):]
-EXTRA_DEP = {"hmx_kernels.hip": _INC + _PLAN, "hmx_tile_bf.hip": [os.path.join(HERE, "csrc", "hmx_kernels.hip")] + _INC + _PLAN, "hmx_api.cpp": _API_INC, "hmx_ranksum.hip": _RANKSUM, "hmx_graph.hip": _GRAPH, "hmx_louvain.hip": _LOUVAIN, "hmx_leiden.hip": _LEIDEN, "hmx_umap.hip": _UMAP, "hmx_umap_transform.hip": _UMAP_TRANSFORM}
+_DOUBLETS = [os.path.join(HERE, "csrc", "hmx_doublets.h"), os.path.join(HERE, "csrc", "hmx_doublet_plan.h"), os.path.join(HERE, "..", "include", "harmony_mi355x_doublets.h")]      # doublet detection: hmx_doublets.hip and hmx_api.cpp only
+_API_INC += _DOUBLETS
+EXTRA_DEP = {"hmx_kernels.hip": _INC + _PLAN, "hmx_tile_bf.hip": [os.path.join(HERE, "csrc", "hmx_kernels.hip")] + _INC + _PLAN, "hmx_api.cpp": _API_INC, "hmx_ranksum.hip": _RANKSUM, "hmx_graph.hip": _GRAPH, "hmx_louvain.hip": _LOUVAIN, "hmx_leiden.hip": _LEIDEN, "hmx_umap.hip": _UMAP, "hmx_umap_transform.hip": _UMAP_TRANSFORM, "hmx_doublets.hip": _DOUBLETS}
 HDR = [os.path.join(HERE, "csrc", "hmx_internal.h"), os.path.join(HERE, "csrc", "hmx_group_plan.h"), os.path.join(HERE, "csrc", "hmx_rrng.h"), os.path.join(HERE, "csrc", "hmx_query_tile.h"), os.path.join(HERE, "csrc", "hmx_dist_tile.h"), os.path.join(HERE, "csrc", "hmx_proj_row.h"), os.path.join(HERE, "..", "include", "harmony_mi355x.h"), os.path.join(HERE, "..", "include", "harmony_mi355x_lab.h"),
        os.path.join(HERE, "..", "include", "harmony_mi355x_metrics.h"), os.path.join(HERE, "..", "include", "harmony_mi355x_silhouette.h"),
        os.path.join(HERE, "..", "include", "harmony_mi355x_confidence.h"), os.path.join(HERE, "..", "include", "harmony_mi355x_project.h"),

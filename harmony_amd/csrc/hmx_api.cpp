@@ -16,6 +16,7 @@
 #include "../../include/harmony_mi355x_leiden.h"  // (Leiden clustering of such a graph: hmx_api_leiden.inc)
 #include "../../include/harmony_mi355x_umap.h"  // (the UMAP layout of such a graph: hmx_api_umap.inc)
 #include "../../include/harmony_mi355x_umap_transform.h"  // (query cells in a fitted layout: hmx_api_umap_transform.inc)
+#include "../../include/harmony_mi355x_doublets.h"  // (doublet detection: hmx_api_doublets.inc)
 #include "hmx_internal.h"
 #include "hmx_rrng.h"
 #include "hmx_plan.h"
@@ -27,6 +28,7 @@
 #include "hmx_leiden.h"
 #include "hmx_umap.h"
 #include "hmx_umap_transform.h"
+#include "hmx_doublets.h"
 #include "hmx_xfer_pool.h"
 
 #include <dlfcn.h>
@@ -388,3 +390,4 @@ int hmx_moe_correct_ridge(hmx_ctx* ctx) {  // src/harmony.cpp:345-638
 #include "hmx_api_leiden.inc"
 #include "hmx_api_umap.inc"
 #include "hmx_api_umap_transform.inc"
+#include "hmx_api_doublets.inc"

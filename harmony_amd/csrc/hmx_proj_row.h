@@ -55,4 +55,34 @@ __device__ __forceinline__ void proj_drain(const float* __restrict__ U, int zs, 
   }
 }
 
+// The wave's queue of contributing (row of the table, weight) pairs in LDS (qj, qw: 128 entries each), shared by k_project and
+// k_doublet_project.  push: the lanes with keep append their (j, w) behind the qn waiting entries in lane order (ballot + prefix count; below =
+// the mask of the lanes under this one); once 64 wait they are drained and the rest moves to the front.  flush: the drain of what is left.
+template <int NC>
+__device__ __forceinline__ void proj_queue_push(int* qj, float* qw, int& qn, unsigned long long below, int lane, bool keep, int j, float w,
+                                                const float* __restrict__ U, int zs, float (&acc)[NC]) {
+  const unsigned long long mask = __ballot(keep);
+  if (keep) {
+    const int at = qn + __popcll(mask & below);
+    qj[at] = j; qw[at] = w;
+  }
+  qn += __popcll(mask);
+  proj_wave_sync();
+  if (qn >= 64) {
+    const int jj = qj[lane]; const float ww = qw[lane];
+    const int rj = qj[64 + lane]; const float rw = qw[64 + lane];
+    proj_wave_sync();
+    qj[lane] = rj; qw[lane] = rw;      // the entries behind the first 64 move to the front
+    qn -= 64;
+    proj_drain<NC>(U, zs, lane, jj, ww, 64, acc);
+    proj_wave_sync();
+  }
+}
+template <int NC>
+__device__ __forceinline__ void proj_queue_flush(const int* qj, const float* qw, int qn, int lane, const float* __restrict__ U, int zs, float (&acc)[NC]) {
+  const int jj = lane < qn ? qj[lane] : 0; const float ww = lane < qn ? qw[lane] : 0.f;
+  proj_wave_sync();
+  proj_drain<NC>(U, zs, lane, jj, ww, qn, acc);
+}
+
 }  // namespace hmx

@@ -13,7 +13,7 @@
 //                       on results, two calls are bit-identical.
 //   Out-of-contract input never leaves the arrays: an indptr pair outside 0 <= lo <= hi <= nnz empties the row, a column outside [0, G_all) or a
 //   negative / non-finite value makes the entry non-contributing, and the kind of violation is or-ed into one flag word the host reads back.
-#include "hmx_proj_row.h"      // (proj_wave_sync, proj_row_total, proj_rate, proj_weight, proj_drain: shared with hmx_pca.hip)
+#include "hmx_proj_row.h"      // (proj_wave_sync, proj_row_total, proj_rate, proj_weight, proj_drain: shared with hmx_pca.hip; the queue: with hmx_doublets.hip)
 
 namespace hmx {
 
@@ -63,30 +63,10 @@ __global__ __launch_bounds__(256) void k_project(ProjDev P) {
         w[s] = proj_weight(x[s], r, P.cap[jc], P.inv_sd[jc]);
       }
 #pragma unroll
-      for (int s = 0; s < PROJ_SWEEPS; s++) {
-        const unsigned long long mask = __ballot(j[s] >= 0);      // (a sweep behind the row's end: no lane)
-        if (j[s] >= 0) {
-          const int at = qn + __popcll(mask & below);
-          qj[wv][at] = j[s]; qw[wv][at] = w[s];
-        }
-        qn += __popcll(mask);
-        proj_wave_sync();
-        if (qn >= 64) {
-          const int jj = qj[wv][lane]; const float ww = qw[wv][lane];
-          const int rj = qj[wv][64 + lane]; const float rw = qw[wv][64 + lane];
-          proj_wave_sync();
-          qj[wv][lane] = rj; qw[wv][lane] = rw;      // the entries behind the first 64 move to the front
-          qn -= 64;
-          proj_drain<NC>(P.U, zs, lane, jj, ww, 64, acc);
-          proj_wave_sync();
-        }
-      }
+      for (int s = 0; s < PROJ_SWEEPS; s++)      // (a sweep behind the row's end: no lane)
+        proj_queue_push<NC>(qj[wv], qw[wv], qn, below, lane, j[s] >= 0, j[s], w[s], P.U, zs, acc);
     }
-    {
-      const int jj = lane < qn ? qj[wv][lane] : 0; const float ww = lane < qn ? qw[wv][lane] : 0.f;
-      proj_wave_sync();
-      proj_drain<NC>(P.U, zs, lane, jj, ww, qn, acc);
-    }
+    proj_queue_flush<NC>(qj[wv], qw[wv], qn, lane, P.U, zs, acc);
 #pragma unroll
     for (int c = 0; c < NC; c++) {
       const int pc = lane + 64 * c;

@@ -373,6 +373,25 @@ if ut:
 else:
     vals["UMAP_TRANSFORM_MEASURED"] = ("**Not measured yet**: `profiles/umap_transform_bench.json` (written by `tools/umap_transform_bench.py` on an MI355X) is not "
                                        "in the tree.")
+db = line("doublets_bench.json")      # tools/doublets_bench.py
+if db:
+    def db_text(r):
+        return ("%s observed cells (%s synthetic, %.0f stored counts per cell): `\"timer:simulate_doublets\"` **%.1f ms** (spread %.0f %%), %.0f ns per synthetic cell; "
+                "the parents' rows read twice are %.1f GB, %.2f ms at %.1f TB/s if all of it came from HBM: **%.1f times the bound**; the same bits in every call: %s"
+                % ("{:,}".format(r["cells"]).replace(",", " "), "{:,}".format(r["n_sim"]).replace(",", " "), r["nnz_per_cell"], r["timer_ms_median"],
+                   100.0 * r["timer_spread"], r["ns_per_synthetic_cell"], r["bytes_parents_read_twice"] / 1e9, r["bound_ms_parents_twice_from_hbm"],
+                   db["hbm_bytes_per_s_assumed"] / 1e12, r["ratio_to_bound"], "yes" if r["same_bits_every_call"] else "NO"))
+    vals["DOUBLETS_MEASURED"] = ("**Measured** (`profiles/doublets_bench.json`, one MI355X, `tools/doublets_bench.py`: G_all = %d, G = %d, d = %d, r = %g, the matrix "
+                                 "device-resident, medians of %d calls after %d; the timer includes the uploads of the tables and the pairs and the download of the "
+                                 "PCs): " % (db["G_all"], db["G"], db["d"], db["ratio"], db["repeats"], db["warmup"]) + "; ".join(db_text(r) for r in db["runs"]) + ".")
+    nb = db.get("neighbors")
+    if nb:
+        vals["DOUBLETS_MEASURED"] += (" `hmx_doublet_neighbors` at %s + %s rows x %d PCs, k_adj = %d: the search `\"timer:knn\"` %.0f ms, the counts behind it "
+                                      "`\"timer:doublet_neighbors\"` %.2f ms." % ("{:,}".format(nb["n_obs"]).replace(",", " "), "{:,}".format(nb["n_sim"]).replace(",", " "),
+                                                                                     nb["d"], nb["k_adj"], nb["knn_ms_median"], nb["count_ms"]))
+else:
+    vals["DOUBLETS_MEASURED"] = ("**Not measured yet**: `profiles/doublets_bench.json` (written by `tools/doublets_bench.py` on an MI355X: the time of "
+                                 "`hmx_simulate_doublets` at 10\u2075 and 10\u2076 observed cells beside the bound of the parents' rows read twice from HBM) is not in the tree.")
 parts = sorted(f for f in os.listdir(os.path.join(ROOT, "docs", "design_parts")) if f.endswith(".md"))
 out = io.StringIO()
 for f in parts:

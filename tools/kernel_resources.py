@@ -16,7 +16,7 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OBJDIR = os.path.join(ROOT, "harmony_amd", "lib", "obj")
 LLVM = "/opt/rocm/lib/llvm/bin"
-OBJECTS = ("hmx_kernels", "hmx_tile_bf", "hmx_seq", "hmx_query", "hmx_confidence", "hmx_project", "hmx_pca", "hmx_ranksum", "hmx_graph", "hmx_louvain", "hmx_leiden", "hmx_umap", "hmx_umap_transform", "hmx_knn", "hmx_silhouette")
+OBJECTS = ("hmx_kernels", "hmx_tile_bf", "hmx_seq", "hmx_query", "hmx_confidence", "hmx_project", "hmx_pca", "hmx_ranksum", "hmx_graph", "hmx_louvain", "hmx_leiden", "hmx_umap", "hmx_umap_transform", "hmx_doublets", "hmx_knn", "hmx_silhouette")
 FIELDS = (".vgpr_count", ".vgpr_spill_count", ".agpr_count", ".sgpr_count", ".sgpr_spill_count", ".private_segment_fixed_size",
           ".group_segment_fixed_size", ".max_flat_workgroup_size")
 
